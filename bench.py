@@ -2,6 +2,7 @@
 """bench.py -- traversed edges/sec (MTEPS), BFS + SSSP on synthetic R-MAT, N x MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scale 22] [--lb block_mapped]
+                    [--dump-outputs DIR] [--full]
 
 One *step* = one BFS followed by one SSSP from the same source (source 0 first, then seeded
 random non-isolated vertices) through the HIP path (`libessentials_amd.so`).  The graph is
@@ -15,7 +16,14 @@ Prints ONE JSON line (rank 0).  N > 1: either launched by
 rank per GPU) with that environment, relays rank 0's line and exits with the children's status.
 GRX_BENCH_BACKEND=gloo rehearses the N > 1 path with the ranks sharing one GPU.
 
-Extra objects on the line (prompt section 4):
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR then
+writes what the last timed step computed (BFS depths as float64, SSSP distances as float32, one
+.npy per array; a fixed seeded sample of the vertices once the full arrays pass 64 MB).
+Everything else on the line -- the extra objects below, the reference-client, direction-optimised
+and PageRank legs, the committed PMC traffic and, at N > 1, the cross-rank verification -- is
+measured only with --full.
+
+Extra objects on the line with --full:
   roofline     dominant kernel = the BFS advance kernels; achieved = algorithmic bytes of one BFS
                (8 B per traversed edge + 20 B per reached vertex) / summed advance
                kernel time of that BFS measured with HIP events on the engine's stream.
@@ -54,7 +62,37 @@ def parse():
     ap.add_argument("--no-pagerank", action="store_true")
     ap.add_argument("--pagerank-scale", type=int, default=24)
     ap.add_argument("--algo", default="bfs+sssp", choices=["bfs+sssp", "bfs", "sssp"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the labels of the last timed step to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the rooflines, side legs, CPU baselines and checks")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir: str, runner, world: int, algo: str) -> None:
+    """What the last timed step handed its caller: the BFS depths (int32, stored as float64, exact)
+    and the SSSP distances (float32), in the graph's vertex numbering.  Past DUMP_MAX_BYTES the
+    same seeded sample of vertices is written for every array, with its ids in sample_index.npy."""
+    import numpy as np
+    arrays = {}
+    if "bfs" in algo:
+        arrays["bfs_depth"] = runner.depth.cpu().numpy().astype(np.float64)
+    if "sssp" in algo:
+        arrays["sssp_distance"] = (runner.distance if world > 1 else runner.dist).cpu().numpy()
+    n = runner.n
+    per_vertex = sum(x.itemsize for x in arrays.values())
+    headers = 4096 * (len(arrays) + 1)
+    if n * per_vertex + headers > DUMP_MAX_BYTES:
+        k = (DUMP_MAX_BYTES - headers) // (per_vertex + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: x[idx] for name, x in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
 
 
 def pick_sources(deg, steps, seed):
@@ -376,8 +414,10 @@ def main():
         dt = float(t.item())
 
     timed_detail = runner.detail()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, runner, world, a.algo)
     # ---- roofline of the dominant kernel (BFS advance), outside the timed region ----
-    roof = runner.bfs_roofline(sources[a.warmup], lb)
+    roof = runner.bfs_roofline(sources[a.warmup], lb) if a.full else None
     out = {
         "metric": "traversed edges/sec (MTEPS) BFS+SSSP on RMAT-%d" % a.scale,
         "value": edges / dt / 1e6,
@@ -400,7 +440,7 @@ def main():
         "roofline": roof,
         "detail": timed_detail,
     }
-    if world == 1 and "sssp" in a.algo:
+    if a.full and world == 1 and "sssp" in a.algo:
         out["roofline_sssp"] = runner.sssp_roofline(sources[a.warmup], lb)
     if world == 1:
         bfs_mean = out["detail"].get("bfs", {}).get("enact_ms_mean_over_timed_steps") or 0.0
@@ -419,19 +459,21 @@ def main():
                               "engine_world_size": job["world_size"], "devices": devs})
         if runner.exchange_note:
             out["config"]["exchange_note"] = runner.exchange_note
-        out["verify"] = runner.verify(sources[a.warmup])
-    if world == 1 and a.algo == "bfs+sssp":
+        if a.full:
+            out["verify"] = runner.verify(sources[a.warmup])
+    if a.full and world == 1 and a.algo == "bfs+sssp":
         out["reference_clients"] = runner.reference_clients(sources[a.warmup:a.warmup + a.steps], lb)
-    if world == 1 and "bfs" in a.algo:
+    if a.full and world == 1 and "bfs" in a.algo:
         out["bfs_direction_optimized"] = runner.bfs_direction_optimized(
             sources[a.warmup:a.warmup + min(a.steps, 8)], lb)
-    if world == 1 and not a.no_pagerank:
+    if a.full and world == 1 and not a.no_pagerank:
         out["pagerank"] = pagerank_leg(ea, ctx, a)
     if world == 1:
         out["runs_in_process"] = dict(runner.runs)   # what a profile of this command contains
-        attach_pmc(out, a, world)
+        if a.full:
+            attach_pmc(out, a, world)
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1:   # timed on the host cores at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:   # timed on the host cores at N = 1 only
             Ap, Aj, Ax = runner.host_csr()
             out["cpu_baseline"] = cpu_baseline(Ap, Aj, Ax, a.algo)
             if "bfs" in a.algo:
@@ -445,7 +487,7 @@ def main():
                 pass
         else:
             out["cpu_baseline"] = None
-            if world > 1:   # timed on the host cores at N = 1 only: carry that run's figures
+            if a.full and world > 1:   # timed on the host cores at N = 1 only: carry that run's figures
                 out["cpu_baseline_n1"] = cpu_baseline_from_n1(a)
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)

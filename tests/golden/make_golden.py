@@ -16,6 +16,9 @@ Inputs:
   * RMAT scale 8..14    -- the build's own generator (oracle/grx_oracle.c), seeds fixed
 Outputs per graph: CSR digests, BFS depths / SSSP distances computed by the
 reference checkers (full arrays when small, sha256 + histogram otherwise).
+Also reference_rmat_ef8.json: the same checkers' answers (sha256) on the seeded
+edge-factor-8 graphs of tests/test_oracle.py::test_live_against_reference_checkers,
+which that test checks the oracle against where oracle/_ref is not built.
 """
 import hashlib
 import json
@@ -59,6 +62,17 @@ def describe(ref, name, Ap, Aj, Ax, sources, full):
     return g
 
 
+LIVE_CASES = ((9, 11, 3), (11, 12, 0), (13, 13, 9))   # (scale, seed, weight seed), edge factor 8
+
+
+def live_cases(o):
+    """(key, CSR, source) of every run test_live_against_reference_checkers makes."""
+    for scale, seed, wseed in LIVE_CASES:
+        n, Ap, Aj, Ax = o.rmat_csr(scale, 8, seed, wseed)
+        for s in np.random.default_rng(seed).integers(0, n, 3):
+            yield f"rmat{scale}_ef8_seed{seed}_w{wseed}_src{int(s)}", (Ap, Aj, Ax), int(s)
+
+
 def main():
     build()
     assert RefOracle.available(), "reference tree not mounted: cannot regenerate goldens"
@@ -95,6 +109,16 @@ def main():
                    "source_of_truth": "reference bfs_cpu.hxx:20-68 / sssp_cpu.hxx:22-72 compiled in place",
                    "graphs": graphs}, f, indent=1)
     print("wrote", len(graphs), "graphs")
+    live = {}
+    for key, (Ap, Aj, Ax), s in live_cases(o):
+        d, _ = ref.bfs(Ap, Aj, s)
+        w, _ = ref.sssp(Ap, Aj, Ax, s)
+        live[key] = {"bfs_sha256": digest(d), "sssp_bits_sha256": digest(w.view(np.uint32))}
+    with open(os.path.join(HERE, "reference_rmat_ef8.json"), "w") as f:
+        json.dump({"generator": "tests/golden/make_golden.py",
+                   "source_of_truth": "reference bfs_cpu.hxx:20-68 / sssp_cpu.hxx:22-72 compiled in place",
+                   "runs": live}, f, indent=1)
+    print("wrote", len(live), "live-test answers")
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runs ON THE GPU BOX (gpurun -- 'bash tools/collect_profiles.sh'): the rocprofv3 passes behind
 # profiles/.
-#   stats   --kernel-trace --stats over the DEFAULT bench command (python3 bench.py): the kernel
+#   stats   --kernel-trace --stats over the full bench command (python3 bench.py --full): the kernel
 #           durations bench.py's live HIP-event numbers must agree with (BFS, SSSP, PageRank).
 #   PMC     SEPARATE --pmc passes (never combined with a trace) over a shorter bench that still
 #           runs every leg: HBM reads by request size (TCC_EA0_RDREQ 32 / 64 / 128 B), the guide's
@@ -13,8 +13,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/profiles_raw
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH_DEFAULT="python3 $ROOT/bench.py"
-BENCH_PMC="python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+BENCH_DEFAULT="python3 $ROOT/bench.py --full"
+BENCH_PMC="python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 echo "[profiles] stats pass: $BENCH_DEFAULT"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- $BENCH_DEFAULT > "$OUT/stats.json" 2> "$OUT/stats.err" || exit 1
 for pass in "rdreq:TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_128B_sum" \

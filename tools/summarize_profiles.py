@@ -148,7 +148,7 @@ with open(PRE + "kernel_by_client.csv", "w", newline="") as f:
         w.writerow([k, c, n, f"{us:.1f}", f"{us / n:.2f}"])
 runs = stats_bench.get("runs_in_process", {})
 pr = stats_bench.get("pagerank", {})
-trace = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py",
+trace = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full",
          "bfs_advance_us_per_traversal": per_client_us["bfs"] / runs["bfs"] if runs.get("bfs") else None,
          "bfs_every_edge_advance_us_per_traversal":
              per_client_us["bfs_every_edge"] / runs["bfs_call_every_edge"] if runs.get("bfs_call_every_edge") else None,
@@ -283,7 +283,7 @@ latest = {
     "round": rnd,
     "git_head": head, "git_dirty_sources": dirty, "kernel_sources_sha": kernel_sources_sha(),
     "command": "tools/collect_profiles.sh: separate rocprofv3 --pmc passes (TCC_EA0_RDREQ by size | FETCH_SIZE | "
-               "WRITE_SIZE | TCC_EA0_WRREQ + atomics | L2 busy | L2 hit) -- python3 bench.py --steps 2 --warmup 1 "
+               "WRITE_SIZE | TCC_EA0_WRREQ + atomics | L2 busy | L2 hit) -- python3 bench.py --full --steps 2 --warmup 1 "
                "--no-cpu-baseline",
     "traffic": tr,
     "calibration_gather_probe": calib,
