@@ -208,6 +208,7 @@ _SIGNATURES = {
     "grx_sssp": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_pagerank": (C.c_int, [_VP, _VP, C.c_float, C.c_float, _VP, C.POINTER(_Options),
                                C.POINTER(_Stats)]),
+    "grx_bc": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -599,6 +600,29 @@ def pagerank(ctx: Context, g: Graph, alpha: float = 0.85, tol: float = 1e-6, p=N
     _check(load_library().grx_pagerank(ctx._h, g._h, alpha, tol, _ptr(p), C.byref(o), C.byref(s)),
            "grx_pagerank")
     return p, Stats._from(s)
+
+
+def bc(ctx: Context, g: Graph, sources=None, bc_values=None, options: Optional[Options] = None):
+    """gunrock::bc::run summed over `sources` -> (float32 centralities on the device, Stats).
+
+    `sources`: None (every vertex), one vertex, or a sequence / numpy array of vertices;
+    bc[v] = 0.5 * sum over the sources s of Brandes' dependency delta_s(v)."""
+    torch = _torch()
+    if bc_values is None:
+        bc_values = torch.empty(g.n_rows, dtype=torch.float32, device=f"cuda:{ctx.device}")
+    if sources is None:
+        h, n = None, 0
+    else:
+        h = np.ascontiguousarray(np.atleast_1d(np.asarray(sources)), dtype=np.int32)
+        if h.ndim != 1:
+            raise ValueError("bc: sources must be one vertex or a flat list of vertices")
+        n = int(h.size)
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_bc(ctx._h, g._h, _ptr(h) if h is not None else None, n, _ptr(bc_values),
+                                 C.byref(o), C.byref(s)), "grx_bc")
+    return bc_values, Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

@@ -233,6 +233,16 @@ int grx_sssp(grx_context_t ctx, grx_graph_t g, int32_t source, float* d_distance
 /* pr::run(G, alpha, tol, p, context)  algorithms/pr.hxx:182-216.  d_p: float[V] out. */
 int grx_pagerank(grx_context_t ctx, grx_graph_t g, float alpha, float tol, float* d_p,
                  const grx_options* opt, grx_stats* stats);
+/* bc::run(G, source, bc_values) summed over a list of sources  algorithms/bc.hxx.
+ * h_sources: HOST int32[n_sources] in the caller's numbering; NULL = every vertex 0..V-1
+ * (n_sources must then be 0).  d_bc: float[V] out, overwritten.  Needs in-edges: an undirected
+ * graph or grx_graph_build_in_edges (GRX_ERR_UNSUPPORTED otherwise, as for pull PageRank).
+ * bc[v] = 0.5 * sum over sources s of delta_s(v) (Brandes, hop counts, edge weights ignored);
+ * the same call on the same handle returns bit-identical values.  opt: read as grx_bfs reads it
+ * for the depth search; max_iterations must be 0.  stats: elapsed_ms (the whole call),
+ * iterations (BFS levels), vertices_reached and edges_traversed, each summed over sources. */
+int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, int32_t n_sources,
+           float* d_bc, const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
