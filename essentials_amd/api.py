@@ -209,6 +209,7 @@ _SIGNATURES = {
     "grx_pagerank": (C.c_int, [_VP, _VP, C.c_float, C.c_float, _VP, C.POINTER(_Options),
                                C.POINTER(_Stats)]),
     "grx_bc": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_tc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -623,6 +624,27 @@ def bc(ctx: Context, g: Graph, sources=None, bc_values=None, options: Optional[O
     _check(load_library().grx_bc(ctx._h, g._h, _ptr(h) if h is not None else None, n, _ptr(bc_values),
                                  C.byref(o), C.byref(s)), "grx_bc")
     return bc_values, Stats._from(s)
+
+
+def tc(ctx: Context, g: Graph, counts=None, per_vertex: bool = True, options: Optional[Options] = None):
+    """gunrock::tc::run on the simple undirected graph under a symmetric CSR -> (int64 per-vertex
+    triangle counts on the device or None, distinct triangles T as an int, Stats).
+
+    `counts`: int64 tensor of V on the context's device, allocated when None; per_vertex=False
+    computes T only (counts is then None).  Self loops and repeated entries are ignored, row order
+    does not matter; the sum of the per-vertex counts is 3 * T."""
+    torch = _torch()
+    if not per_vertex:
+        counts = None
+    elif counts is None:
+        counts = torch.empty(g.n_rows, dtype=torch.int64, device=f"cuda:{ctx.device}")
+    total = C.c_uint64()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_tc(ctx._h, g._h, _ptr(counts), C.byref(total), C.byref(o), C.byref(s)),
+           "grx_tc")
+    return counts, int(total.value), Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

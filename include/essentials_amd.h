@@ -243,6 +243,27 @@ int grx_pagerank(grx_context_t ctx, grx_graph_t g, float alpha, float tol, float
  * iterations (BFS levels), vertices_reached and edges_traversed, each summed over sources. */
 int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, int32_t n_sources,
            float* d_bc, const grx_options* opt, grx_stats* stats);
+/* tc::run(G, reduce_all_triangles, vertex_triangles_count, &total)  algorithms/tc.hxx
+ * Counts the triangles of the SIMPLE UNDIRECTED graph under the CSR: self loops are ignored,
+ * repeated entries of a row count once, and row order does not matter (unsorted rows give the
+ * same answer).  d_vertex_triangles: device int64[V] out, overwritten with the number of triangles
+ * that contain each vertex (the caller's numbering); NULL = the total only.  h_triangles: HOST
+ * out, the number of DISTINCT triangles T (the reference's total_triangles_count is the sum of
+ * its per-vertex counts, 3 * T); NULL = per-vertex counts only.  At least one of the two outputs
+ * must be non-NULL (GRX_ERR_INVALID_ARGUMENT otherwise).  On a graph whose rows are sorted and
+ * free of repeats (self loops allowed) the per-vertex counts equal the reference's
+ * vertex_triangles_count, and its total equals 3 * T; the per-vertex counts are 64-bit on purpose
+ * (the reference's int32 can overflow on hubs).  Undirected input only: n_rows != n_cols is
+ * GRX_ERR_INVALID_ARGUMENT; a handle with in-edges attached, or a CSR that is not its own
+ * transpose (verified once when unknown), is GRX_ERR_UNSUPPORTED.  opt may be NULL; only
+ * collect_kernel_time is read.  stats may be NULL; set: elapsed_ms (the whole call),
+ * advance_kernel_ms (the counting kernels alone, when collect_kernel_time is set), iterations (1),
+ * edges_traversed (oriented edges = simple undirected edges that are not self loops) and
+ * edges_expanded (intersection work: neighbour-list entries probed).  The call leaves no state on
+ * the handle but the symmetry verdict (no hot-first copy is built); its workspace is released
+ * when it returns.  Same call, same results (integer sums). */
+int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triangles,
+           uint64_t* h_triangles, const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
