@@ -32,9 +32,10 @@ extern "C" int grx_bfs(grx_context_t ctx, grx_graph_t g, int32_t source, int32_t
       graph_type G = run_on->view();
       problem_type problem(G, run_on == g ? source : g->hot_rank_of[(std::size_t)source], d_distances,
                            ctx->mc);
-      if (run_on != g)
+      if (run_on != g) {
         problem.scatter_to = g->hot_vertex_of.data();
         problem.gather_from = g->hot_rank_of_device.data();
+      }
       // push search: one byte per vertex while it runs once 4-byte depths outgrow the eight L2s
       // (GRX_BFS_BYTE_LABELS=0/1 overrides; measurements in DESIGN.md, "Larger graphs")
       if (!o.direction_optimized) {
@@ -80,8 +81,10 @@ extern "C" int grx_bfs(grx_context_t ctx, grx_graph_t g, int32_t source, int32_t
         // came with the degree sum of its vertices: the counts are sums over the level log, the
         // source's degree was left in pinned memory by the reset pass -- no statistics pass
         const unsigned long long* facts = ctx->single().workspace().run_facts();
+        // (not on a renumbered copy with sinks: a label-scan level labels them without ever putting
+        // them into a frontier, so the frontier lengths undercount what was reached)
         if (!o.direction_optimized && !o.holes_layout && o.max_iterations == 0 &&
-            problem.log.unknown_work_levels == 1) {
+            problem.log.unknown_work_levels == 1 && !(run_on != g && run_on->edges_into_tail)) {
           stats->vertices_reached = problem.log.slots_total;
           stats->edges_traversed = problem.log.edges_expanded + (long long)facts[0];
           stats->edges_expanded = stats->edges_traversed;

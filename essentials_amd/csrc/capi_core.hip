@@ -132,6 +132,13 @@ grx_graph_s* essentials_amd::hot_copy(grx_context_s* ctx, grx_graph_s* g, bool c
         (std::size_t)g->n_rows,
         [hap] __device__(std::size_t i) -> unsigned long long { return hap[i + 1] > hap[i] ? 1ull : 0ull; },
         0ull, rocprim::plus<unsigned long long>(), ctx->single());
+    const int32_t* haj = h->d_aj;
+    const int32_t lead = (int32_t)h->leading_connected;
+    if (h->leading_connected < (unsigned long long)g->n_rows)
+      h->edges_into_tail = hip::transform_reduce(
+          (std::size_t)g->nnz,
+          [haj, lead] __device__(std::size_t e) -> unsigned long long { return haj[e] >= lead ? 1ull : 0ull; },
+          0ull, rocprim::plus<unsigned long long>(), ctx->single());
   }
   g->hot_rank_of.resize((std::size_t)g->n_rows);
   GRX_HIP_CHECK(hipMemcpy(g->hot_rank_of.data(), R.rank_of.data(), (std::size_t)g->n_rows * 4,

@@ -131,6 +131,9 @@ struct grx_graph_s {
   bool renumbered_slice = false;
   // a renumbered copy: its vertices with edges come first, this many of them (0 = not such a copy)
   unsigned long long leading_connected = 0;
+  // ... and how many of its edges lead to a vertex beyond them: a directed graph's sinks.  A label
+  // scan stops at leading_connected, so a sink it leaves out is labelled but never in a frontier.
+  unsigned long long edges_into_tail = 0;
 
   essentials_amd::graph_type view() const {
     using namespace gunrock;

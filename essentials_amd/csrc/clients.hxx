@@ -228,8 +228,11 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
       if (ctx->options().label_scan_min_work && work >= ctx->options().label_scan_min_work) {
         // the widest levels: no output frontier at all -- the labels say what the level found, and
         // one pass over them builds the next frontier in ascending runs with its degree sum
-        // (operators::filter::select_range; the graph's vertices without edges are skipped when a
-        // hot-first numbering put them last)
+        // (operators::filter::select_range).  On a hot-first copy only the ids below leading_connected
+        // are candidates: what lies beyond has no out-edges -- isolated vertices, and on a directed
+        // graph the sinks, which ARE discovered (the advance labels them) but expand nothing, so the
+        // next frontier does not need them; the bitmap side product still covers them, select_range
+        // visits every id below bit_limit.
         // Nobody reads this level's output, so nobody needs to know WHO reached a vertex first: every
         // arrival that finds it unlabelled writes the same depth.  `mark` is a plain conditional
         // store where visit() is a fresh look + a read-modify-write at the memory side (27 G/s on this
@@ -546,6 +549,12 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
   // iterations run at the fabric's rate of 128-byte label lines).
   hip::device_array_t<unsigned short> bound16;
   bool bounds_fresh = false;  // the previous iteration's label scan has just written them
+  // The scan visits the ids below leading_connected only.  On a directed hot-first copy the ids beyond
+  // it include sinks (in-edges, no out-edges), which ARE destinations: their bounds are written by
+  // snapshot_bounds() alone.  Once one snapshot has covered every id the scan's refresh is enough --
+  // labels only fall, so a sink's older bound stays an upper bound; before that the scan leaves
+  // bound16[sink] as resize() left it and the bounds do not count as fresh.
+  bool bounds_complete = false;
   // renumbered graph (see bfs_problem_t): distances are delivered as distance[scatter_to[v]], or
   // gathered through the inverse permutation when the owner has it on the device
   const vertex_t* scatter_to = nullptr;
@@ -603,11 +612,13 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
           b[i] = (unsigned short)(up > 0xffffu ? 0xffffu : up);
         },
         ctx->stream());
+    bounds_complete = true;
   }
   void reset() override {
     auto ctx = this->get_single_context();
     const std::size_t n = (std::size_t)this->get_graph().get_number_of_vertices();
     const vertex_t s = source;
+    bounds_fresh = bounds_complete = false;  // bound16 describes the labels of an earlier run, or nothing
     if (packed_labels) {
       unsigned long long* p = packed.data();
       const unsigned long long zero = (unsigned long long)ordered_bits(weight_t(0)) << 32;
@@ -682,6 +693,7 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
   bool bound_filter = true;  // wide iterations: 2-byte bound mirror in front of the labels (packed form)
   int bound_from = -1;       // >= 0: first iteration that uses it (experiments); -1: by edges expanded so far
   bool early_live = true;    // the batched form before that point too (hot-first graphs), live labels beyond the image
+  const bool debug = std::getenv("GRX_DEBUG") != nullptr;  // read once per run: one line per iteration
 
   sssp_enactor_t(problem_type* p, std::shared_ptr<gcuda::multi_context_t> ctx,
                  enactor_properties_t props = enactor_properties_t())
@@ -712,7 +724,10 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
       return (unsigned)packed[v] == this_round;
     };
     // the same pass leaves the next iteration's 2-byte bounds (snapshot_bounds() of the labels as
-    // they stand now); vertices without edges are never a destination, their bounds are not read
+    // they stand now) for the ids it visits.  The ids beyond n_scan have no out-edges: isolated
+    // vertices are never a destination, but a directed graph's sinks are, and their bounds ARE read.
+    // Skipping them is safe only after one full snapshot_bounds(): labels only fall, so the bound it
+    // left for a sink still is an upper bound (a weaker filter, never a wrong rejection).
     unsigned short* bound16 = P->bound16.data();
     auto bound_of = [packed, bound16] __device__(vertex_t const& v) {
       const unsigned bits = (unsigned)(packed[v] >> 32);
@@ -720,8 +735,21 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
       bound16[v] = (unsigned short)(up > 0xffffu ? 0xffffu : up);
     };
     operators::filter::select_range(G, n_scan, lowered_now, *E->get_output_frontier(), *ctx, bound_of);
-    P->bounds_fresh = true;
+    P->bounds_fresh = n_scan == (std::size_t)G.get_number_of_vertices() || P->bounds_complete;
     E->swap_frontier_buffers();
+  }
+
+  /// GRX_DEBUG: which form this iteration takes.  Packed labels: A plain,
+  /// B label scan, C bounded, D bounded + scan, E early-live (`scan`: it ran without an output and the
+  /// label scan built the next frontier; `snapshot`: snapshot_bounds() ran first).  T: the reference's
+  /// two-pass formulation, W: distance and stamp in two words.
+  void note_form(char form, bool scan, bool snapshot) {
+    if (!debug)
+      return;
+    auto in = this->get_enactor()->get_input_frontier();
+    std::fprintf(stderr, "[grx] sssp iteration %d: form %c scan %d snapshot %d slots %zu work %lld\n",
+                 (int)this->iteration, form, (int)scan, (int)snapshot, (std::size_t)in->get_number_of_elements(),
+                 in->work_hint() == frontier_t::unknown_work ? -1ll : (long long)in->work_hint());
   }
 
   void loop(gcuda::multi_context_t& context) override {
@@ -755,6 +783,7 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
         stamp[v] = round;
         return true;
       };
+      note_form('T', false, false);
       operators::advance::execute<lb>(G, E, relax_all, context);
       operators::filter::execute<operators::filter_algorithm_t::bypass>(G, E, once, context);
       return;
@@ -833,7 +862,8 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
             ctx->options().settled_filter &&
             !ctx->options().holes_layout && work != frontier_t::unknown_work &&
             work >= ctx->options().settled_min_work) {
-          if (!P->bounds_fresh) {  // part of this iteration's advance: timed with it when kernels are timed
+          const bool snapshot = !P->bounds_fresh;
+          if (snapshot) {  // part of this iteration's advance: timed with it when kernels are timed
             operators::advance::detail::clocked_t clock(*ctx);
             P->snapshot_bounds();
             clock.stop();
@@ -850,6 +880,7 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
             return b != 0xffffu && problem_type::ordered_bits(through) >= (b << 16);
           };
           const bool scan = ctx->options().label_scan_min_work && work >= ctx->options().label_scan_min_work;
+          note_form(reached_enough ? (scan ? 'D' : 'C') : 'E', scan, snapshot);
           auto run = [&](auto hinted) {
             if (scan) {
               // no output frontier: the round tag in a label's low word says "lowered in this round"
@@ -889,6 +920,7 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
         if (lb == load_balance_t::block_mapped && !ctx->options().holes_layout &&
             ctx->options().label_scan_min_work && work != frontier_t::unknown_work &&
             work >= ctx->options().label_scan_min_work) {
+          note_form('B', true, false);
           ctx->options().defer_sync_of_none_output = true;  // scan_improved below is its hand-off
           operators::advance::execute<lb, operators::advance_direction_t::forward,
                                       operators::advance_io_type_t::vertices,
@@ -898,9 +930,11 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
           return;
         }
       }
+      note_form('A', false, false);
       operators::advance::execute<lb>(G, E, relax_packed, context);
       return;
     }
+    note_form('W', false, false);
     auto relax = [distance, stamp, round] __host__ __device__(
                      vertex_t const& src, vertex_t const& dst, edge_t const& edge,
                      weight_t const& w) -> bool {
