@@ -197,6 +197,7 @@ _SIGNATURES = {
     "grx_graph_rmat": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int,
                                  C.POINTER(_VP)]),
     "grx_graph_sorted_rows": (C.c_int, [_VP, _VP, C.POINTER(_VP)]),
+    "grx_graph_simple": (C.c_int, [_VP, _VP, C.POINTER(_VP)]),
     "grx_graph_build_in_edges": (C.c_int, [_VP, _VP]),
     "grx_graph_hot_first": (C.c_int, [_VP, _VP, C.c_int]),
     "grx_graph_destroy": (C.c_int, [_VP]),
@@ -210,6 +211,7 @@ _SIGNATURES = {
                                C.POINTER(_Stats)]),
     "grx_bc": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_tc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_kcore": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -516,6 +518,13 @@ class Graph:
                "grx_graph_sorted_rows")
         return Graph(h)
 
+    def simple(self, ctx: "Context") -> "Graph":
+        """The simple graph under this one: self loops dropped, repeated entries kept once (smallest
+        weight of the repeats), rows sorted by column id."""
+        h = _VP()
+        _check(load_library().grx_graph_simple(ctx._h, self._h, C.byref(h)), "grx_graph_simple")
+        return Graph(h)
+
     def build_in_edges(self, ctx: "Context") -> "Graph":
         """Attach the transpose (in-edges) of a DIRECTED graph: enables pull / direction-optimised BFS."""
         _check(load_library().grx_graph_build_in_edges(ctx._h, self._h), "grx_graph_build_in_edges")
@@ -645,6 +654,26 @@ def tc(ctx: Context, g: Graph, counts=None, per_vertex: bool = True, options: Op
     _check(load_library().grx_tc(ctx._h, g._h, _ptr(counts), C.byref(total), C.byref(o), C.byref(s)),
            "grx_tc")
     return counts, int(total.value), Stats._from(s)
+
+
+def kcore(ctx: Context, g: Graph, cores=None, options: Optional[Options] = None):
+    """gunrock::kcore::run on a symmetric CSR -> (int32 core numbers on the device, degeneracy as an
+    int, Stats).
+
+    `cores`: int32 tensor of V on the context's device, allocated when None.  Every entry of the CSR
+    counts (repeats each time, a self loop once): `g.simple(ctx)` gives the textbook core numbers
+    of the simple graph under a multigraph.  Stats.iterations is the number of distinct non-zero
+    core values and Stats.edges_expanded equals nnz (every row is walked once)."""
+    torch = _torch()
+    if cores is None:
+        cores = torch.empty(g.n_rows, dtype=torch.int32, device=f"cuda:{ctx.device}")
+    degeneracy = C.c_int32()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_kcore(ctx._h, g._h, _ptr(cores), C.byref(degeneracy), C.byref(o), C.byref(s)),
+           "grx_kcore")
+    return cores, int(degeneracy.value), Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

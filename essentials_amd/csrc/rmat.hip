@@ -205,6 +205,95 @@ extern "C" int grx_graph_sorted_rows(grx_context_t ctx, grx_graph_t g, grx_graph
   });
 }
 
+namespace {
+/// 1 where entry e of the (row, column)-sorted keys stays in the simple graph: the first of its
+/// run of repeats, and not a self loop.  e == nnz (the scan's total slot) -> 0.
+struct simple_keep_t {
+  const unsigned long long* keys;
+  long long nnz;
+  __host__ __device__ int operator()(long long e) const {
+    if (e >= nnz)
+      return 0;
+    const unsigned long long key = keys[e];
+    return (unsigned)(key >> 32) != (unsigned)key && (e == 0 || keys[e - 1] != key);
+  }
+};
+/// Kept entries to their places: column, and the smallest weight of the run of repeats.
+__global__ void __launch_bounds__(256)
+    simple_write_kernel(const unsigned long long* keys, const float* ax, const int* at, long long nnz, int* aj_out,
+                        float* ax_out) {
+  for (long long e = blockIdx.x * 256ll + threadIdx.x; e < nnz; e += (long long)gridDim.x * 256) {
+    if (at[e + 1] == at[e])
+      continue;
+    const unsigned long long key = keys[e];
+    float w = ax[e];
+    for (long long r = e + 1; r < nnz && keys[r] == key; ++r)
+      w = fminf(w, ax[r]);
+    aj_out[at[e]] = (int)(unsigned)key;
+    ax_out[at[e]] = w;
+  }
+}
+/// Sorting keeps every row where it was: the new offset of a row is the kept entries before it.
+__global__ void __launch_bounds__(256) simple_offsets_kernel(const int* ap, const int* at, int n_rows, int* ap_out) {
+  for (long long r = blockIdx.x * 256ll + threadIdx.x; r <= n_rows; r += (long long)gridDim.x * 256)
+    ap_out[r] = at[ap[r]];
+}
+}  // namespace
+
+extern "C" int grx_graph_simple(grx_context_t ctx, grx_graph_t g, grx_graph_t* out) {
+  if (!ctx || !g || !out)
+    return invalid("grx_graph_simple: NULL argument");
+  return guarded([&] {
+    auto& c = ctx->single();
+    hipStream_t s = c.stream();
+    auto r = std::make_unique<grx_graph_s>();
+    r->n_rows = g->n_rows;
+    r->n_cols = g->n_cols;
+    r->symmetry = g->symmetry;  // dropping loops and repeats keeps (a)symmetry
+    r->ap.resize((std::size_t)g->n_rows + 1);
+    const std::size_t nnz = (std::size_t)g->nnz;
+    int kept = 0;
+    if (nnz) {
+      hip::buffer_t<unsigned long long> keys(nnz), keys2(nnz);
+      hip::buffer_t<float> ax2(nnz);
+      hip::buffer_t<int> at(nnz + 1);
+      const unsigned grid = (unsigned)c.compute_units() * 8;
+      row_col_keys_kernel<<<grid, 256, 0, s>>>(g->d_ap, g->d_aj, g->n_rows, (long long)nnz, keys.data());
+      GRX_HIP_CHECK(hipGetLastError());
+      std::size_t bytes = 0, scan_bytes = 0;
+      GRX_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys.data(), keys2.data(), g->d_ax, ax2.data(), nnz, 0,
+                                              64, s));
+      auto keep = rocprim::make_transform_iterator(rocprim::make_counting_iterator<long long>(0),
+                                                   simple_keep_t{keys2.data(), (long long)nnz});
+      scan_bytes = hip::exclusive_sum_temp_bytes(keep, at.data(), 0, nnz + 1);
+      bytes = std::max(bytes, scan_bytes);
+      hip::buffer_t<unsigned char> temp(bytes < 256 ? 256 : bytes);  // never null: rocPRIM would only size
+      GRX_HIP_CHECK(rocprim::radix_sort_pairs(temp.data(), bytes, keys.data(), keys2.data(), g->d_ax, ax2.data(), nnz,
+                                              0, 64, s));
+      hip::exclusive_sum(temp.data(), bytes, keep, at.data(), 0, nnz + 1, s);
+      GRX_HIP_CHECK(hipMemcpyAsync(&kept, at.data() + nnz, sizeof kept, hipMemcpyDeviceToHost, s));
+      GRX_HIP_CHECK(hipStreamSynchronize(s));
+      r->aj.resize((std::size_t)std::max(kept, 1));
+      r->ax.resize((std::size_t)std::max(kept, 1));
+      simple_write_kernel<<<grid, 256, 0, s>>>(keys2.data(), ax2.data(), at.data(), (long long)nnz, r->aj.data(),
+                                               r->ax.data());
+      simple_offsets_kernel<<<grid, 256, 0, s>>>(g->d_ap, at.data(), g->n_rows, r->ap.data());
+      GRX_HIP_CHECK(hipGetLastError());
+      GRX_HIP_CHECK(hipStreamSynchronize(s));
+    } else {
+      r->aj.resize(1);
+      r->ax.resize(1);
+      GRX_HIP_CHECK(hipMemsetAsync(r->ap.data(), 0, ((std::size_t)g->n_rows + 1) * 4, s));
+      GRX_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    r->nnz = kept;
+    r->adopt();
+    *out = r.release();
+    hip::block_cache_t::instance().trim();  // the sort's key buffers, see grx_graph_rmat
+    return (int)GRX_OK;
+  });
+}
+
 extern "C" int grx_graph_rmat(grx_context_t ctx, uint32_t scale, uint32_t edge_factor,
                               uint64_t seed, uint64_t weight_seed, int symmetrize,
                               grx_graph_t* out) {

@@ -198,6 +198,12 @@ int grx_graph_rmat(grx_context_t ctx, uint32_t scale, uint32_t edge_factor, uint
  * EMISSION order inside a row (an unsorted edge-list file); this utility produces the other
  * common layout of the same graph. */
 int grx_graph_sorted_rows(grx_context_t ctx, grx_graph_t g, grx_graph_t* out);
+/* Owning copy of `g` as a SIMPLE graph: self loops dropped, repeated entries of a row kept once
+ * (weight: the smallest of the repeats, so that SSSP distances are unchanged), rows sorted by
+ * column.  A symmetric input gives a symmetric output, and the copy carries the input's symmetry
+ * verdict when it is known.  The layout on which grx_kcore returns the textbook core numbers and
+ * grx_tc's per-vertex counts equal the reference's. */
+int grx_graph_simple(grx_context_t ctx, grx_graph_t g, grx_graph_t* out);
 /* Build and attach the in-edge (transpose / csc) arrays of a DIRECTED graph so that pull advances
  * (grx_options.direction_optimized) can walk in-neighbours; graphs without them are taken to be
  * undirected (symmetric CSR = its own transpose).  Reference counterpart: the csc view of
@@ -264,6 +270,34 @@ int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, int32_t n
  * when it returns.  Same call, same results (integer sums). */
 int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triangles,
            uint64_t* h_triangles, const grx_options* opt, grx_stats* stats);
+/* kcore::run(G, k_cores)  algorithms/kcore.hxx
+ * Core numbers by peeling THE CSR AS IT IS GIVEN, every entry counting: the degree of v is the
+ * length of row v, a repeated entry counts each time it appears, and a self loop counts as the one
+ * entry it is and is never taken away before its vertex leaves.  core[v] is the value of k at which
+ * v leaves when, for k = 1, 2, ..., vertices of remaining degree <= k are removed until none is
+ * left, each removal lowering the remaining degree of the vertex named by every entry of the
+ * removed row.  That is what kcore.hxx and the reference's kcore_cpu.hxx compute, so on any
+ * symmetric CSR d_core equals the reference's k_cores; on a simple graph (no repeats, no self
+ * loops) it is the textbook core number.  The result does not depend on the order of removals or of
+ * a row's entries: the same call returns identical values.  The call does NOT deduplicate (the
+ * R-MAT generator emits a multigraph whose degeneracy by entries is about twice the simple graph's):
+ * a caller who wants the simple graph's core numbers passes grx_graph_simple of the handle.
+ * d_core: device int32[V] out, overwritten, the caller's numbering; a vertex with an empty row gets
+ * 0.  h_degeneracy: HOST out, the largest core number (0 for a graph without entries).  At least
+ * one of the two must be non-NULL (GRX_ERR_INVALID_ARGUMENT otherwise); with d_core == NULL the call
+ * uses a workspace of its own.  Undirected input only: n_rows != n_cols is
+ * GRX_ERR_INVALID_ARGUMENT; a handle with in-edges attached, or a CSR that is not its own transpose
+ * (verified once when unknown), is GRX_ERR_UNSUPPORTED.  opt may be NULL; only collect_kernel_time
+ * is read, and max_iterations != 0 is GRX_ERR_INVALID_ARGUMENT.  stats may be NULL; set: elapsed_ms
+ * (the whole call), advance_kernel_ms (the peeling kernels, batch by batch, when
+ * collect_kernel_time is set), advance_launches (kernel launches of the peel), iterations (the
+ * number of DISTINCT NON-ZERO core values: defined by the answer, not by the schedule),
+ * vertices_reached (vertices with a non-empty row), edges_traversed = edges_expanded (row entries
+ * walked: each row is walked once, when its vertex leaves, so this equals nnz).  The call leaves no
+ * state on the handle but the symmetry verdict (no hot-first copy is built or used); its workspace
+ * is released when it returns. */
+int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int32_t* h_degeneracy,
+              const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
