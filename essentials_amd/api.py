@@ -212,6 +212,7 @@ _SIGNATURES = {
     "grx_bc": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_tc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_kcore": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_cc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -674,6 +675,35 @@ def kcore(ctx: Context, g: Graph, cores=None, options: Optional[Options] = None)
     _check(load_library().grx_kcore(ctx._h, g._h, _ptr(cores), C.byref(degeneracy), C.byref(o), C.byref(s)),
            "grx_kcore")
     return cores, int(degeneracy.value), Stats._from(s)
+
+
+def cc(ctx: Context, g: Graph, components=None, options: Optional[Options] = None):
+    """Connected components (weakly connected on a directed CSR) -> (int32 labels on the device,
+    number of components as an int, Stats).
+
+    labels[v] is the smallest vertex id of the component that holds v, so labels[v] == v marks a
+    component's representative and `torch.bincount(labels)` gives the component sizes.
+    `components`: int32 contiguous tensor of V on the context's device, allocated when None.
+    Stats.vertices_reached is V - components; Stats.edges_expanded counts the row entries read, nnz
+    unless the graph is known to be symmetric, when the rows of the largest component stay unread."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if components is None:
+        components = torch.empty(g.n_rows, dtype=torch.int32, device=device)
+    else:
+        if not isinstance(components, torch.Tensor) or components.dtype != torch.int32:
+            raise TypeError("cc: components must be an int32 torch tensor")
+        if components.dim() != 1 or components.numel() != g.n_rows or not components.is_contiguous():
+            raise ValueError(f"cc: components must be a contiguous tensor of {g.n_rows} elements")
+        if components.device != device:
+            raise ValueError(f"cc: components must live on {device}")
+    count = C.c_int64()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_cc(ctx._h, g._h, _ptr(components), C.byref(count), C.byref(o), C.byref(s)),
+           "grx_cc")
+    return components, int(count.value), Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

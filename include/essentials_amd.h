@@ -298,6 +298,40 @@ int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triangles,
  * is released when it returns. */
 int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int32_t* h_degeneracy,
               const grx_options* opt, grx_stats* stats);
+/* Connected components (no reference counterpart: the reference has no such algorithm).
+ * Every row entry (u, v) joins u and v, whatever its direction: on a symmetric CSR the result is
+ * the connected components, on a directed one the WEAKLY connected components.  Self loops and
+ * repeated entries change nothing.  d_component: device int32[V] out, overwritten;
+ * d_component[v] is the SMALLEST VERTEX ID, in the caller's numbering, of the component that holds
+ * v.  Hence d_component[v] <= v, v is its component's representative iff d_component[v] == v, and
+ * the result is a function of the graph alone: not of the schedule, the order of a row's entries,
+ * the sampling below or a hot-first copy.  The same call returns bit-identical values.
+ * h_components: HOST out, the number of components (an isolated vertex is one).  At least one of
+ * the two must be non-NULL (GRX_ERR_INVALID_ARGUMENT otherwise); with d_component == NULL the call
+ * uses a workspace of its own.  A directed CSR is supported and needs no in-edges (attached ones
+ * are ignored); n_rows != n_cols is GRX_ERR_INVALID_ARGUMENT; V == 0 is GRX_OK with
+ * *h_components = 0 and nothing written.  opt may be NULL; only collect_kernel_time is read, and
+ * max_iterations != 0 is GRX_ERR_INVALID_ARGUMENT.
+ * Method: Afforest -- lock-free union-find on d_component itself (the larger root is hooked under
+ * the smaller by a 32-bit compare-and-swap, so a tree's root is its smallest member), two neighbour
+ * rounds (round r hooks every vertex to entry r of its row; GRX_CC_SAMPLE_ROUNDS = 0..8 overrides,
+ * 0 = hook every entry), then a remainder pass over the other entries that LEAVES THE ROWS OF THE
+ * MOST FREQUENT COMPONENT UNREAD.  That skip is sound only when every edge is stored from both
+ * ends, so it is taken only when the handle's symmetry verdict is already "symmetric" (R-MAT with
+ * symmetrize, symmetric Matrix Market files, handles another call has verified) and no in-edges
+ * are attached; the call does not start the verification itself.  Otherwise every row is walked in
+ * full.  stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels alone,
+ * when collect_kernel_time is set), advance_launches (kernel launches), iterations (passes over
+ * neighbour positions: the neighbour rounds + the remainder pass -- defined by the schedule, not
+ * by the answer), vertices_reached (V - components: vertices that are not their component's
+ * representative), edges_traversed = edges_expanded (row entries the hooking kernels read: nnz
+ * when every row is walked, a small part of it when the skip applies; with the skip a vertex that
+ * joins the picked component while the remainder pass runs may or may not have its row read, so
+ * this figure can differ by a few rows between calls -- the labels cannot).  The call runs on the
+ * caller's CSR as given, builds and uses no hot-first copy, leaves nothing on the handle and
+ * releases its workspace when it returns. */
+int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_components,
+           const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
