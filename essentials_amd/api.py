@@ -213,6 +213,8 @@ _SIGNATURES = {
     "grx_tc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_kcore": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_cc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_mst": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP,
+                          C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -704,6 +706,48 @@ def cc(ctx: Context, g: Graph, components=None, options: Optional[Options] = Non
     _check(load_library().grx_cc(ctx._h, g._h, _ptr(components), C.byref(count), C.byref(o), C.byref(s)),
            "grx_cc")
     return components, int(count.value), Stats._from(s)
+
+
+def mst(ctx: Context, g: Graph, entries=None, components=None, options: Optional[Options] = None):
+    """Minimum spanning forest of the CSR as given -> (int32 chosen entry positions on the device,
+    ascending; their total weight as a float; int32 component labels or None; Stats).
+
+    Every row entry is an undirected candidate, ordered by (weight, position): the result is what
+    Kruskal accepts in that order (include/essentials_amd.h).  The returned `entries` is the tensor
+    sliced to the count, V - components; position e is an index into the column and value arrays.
+    `entries`: int32 contiguous tensor of V on the context's device, allocated when None and filled
+    in place otherwise.  `components`: None (no labels), True (allocate them) or such a tensor of
+    V; the labels are those of `cc`.  Stats.iterations is the number of Boruvka rounds and
+    Stats.edges_expanded the row entries the minimum search read, summed over rounds."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+
+    def checked(t, what):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError(f"mst: {what} must be an int32 torch tensor")
+        if t.dim() != 1 or t.numel() != g.n_rows or not t.is_contiguous():
+            raise ValueError(f"mst: {what} must be a contiguous tensor of {g.n_rows} elements")
+        if t.device != device:
+            raise ValueError(f"mst: {what} must live on {device}")
+        return t
+
+    if entries is None:
+        entries = torch.empty(g.n_rows, dtype=torch.int32, device=device)
+    else:
+        checked(entries, "entries")
+    if components is True:
+        components = torch.empty(g.n_rows, dtype=torch.int32, device=device)
+    elif components is False:
+        components = None
+    elif components is not None:
+        checked(components, "components")
+    count, weight = C.c_int64(), C.c_double()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_mst(ctx._h, g._h, _ptr(entries), C.byref(count), C.byref(weight),
+                                  _ptr(components), C.byref(o), C.byref(s)), "grx_mst")
+    return entries[: count.value], float(weight.value), components, Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

@@ -332,6 +332,49 @@ int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int32_t* h_dege
  * releases its workspace when it returns. */
 int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_components,
            const grx_options* opt, grx_stats* stats);
+/* Minimum spanning FOREST of the CSR as given (the reference's mst.hxx returns one float total,
+ * accumulated by float atomics, on connected graphs only, and no edges; this is not a port of it).
+ * Every row entry e = (u, v, w) is an undirected candidate edge, whatever its direction; e is the
+ * entry's position in the column array.  A directed CSR therefore gives the forest of its weak
+ * components and needs no in-edges (attached ones are ignored).  Self loops are never chosen.
+ * Repeated entries and the two stored directions of a symmetric edge are separate entries and
+ * compete like any others.  Entries are strictly and totally ordered by the 64-bit key
+ *     key(e) = (ordered_bits(w) << 32) | e
+ * where ordered_bits maps a float's bit pattern b to ~b when its sign bit is set and to
+ * b | 0x80000000 otherwise: monotone in the value, -0 below +0; the place of a NaN weight is
+ * unspecified.  THE RESULT IS EXACTLY THE SET OF ENTRIES KRUSKAL ACCEPTS WHEN IT TAKES ENTRIES IN
+ * ASCENDING KEY: a function of the CSR arrays alone, not of the schedule, and the same call returns
+ * bit-identical outputs.  When weights tie, the chosen entries depend on the row layout (positions
+ * break the ties); the total weight does not.  Every handle with entries carries values (the
+ * constructors demand them), and they are read as grx_sssp reads them: as they are.
+ * d_entries: device int32[V] out or NULL: the chosen entry positions in ASCENDING order, the first
+ * *h_count of them valid, the rest untouched.  h_count: HOST out or NULL: the number of chosen
+ * entries = V - components.  h_weight: HOST out or NULL: the float64 sum of the chosen weights, added
+ * in ascending entry order by a fixed tree (no float atomics), so it is reproducible, and exact
+ * whenever the float64 sum of these float32 values is.  d_component: device int32[V] out or NULL:
+ * the labels grx_cc returns (the smallest vertex id of each vertex's component).  At least one of
+ * the four must be non-NULL (GRX_ERR_INVALID_ARGUMENT otherwise); the call works on arrays of its own
+ * either way.  n_rows != n_cols is GRX_ERR_INVALID_ARGUMENT; V == 0 is GRX_OK with count 0, weight
+ * 0.0 and nothing written.  opt may be NULL; only collect_kernel_time is read, and
+ * max_iterations != 0 is GRX_ERR_INVALID_ARGUMENT.
+ * Method: Boruvka.  Each round, every entry whose ends lie in different components offers its key to
+ * BOTH components (pre-tested 64-bit atomic min; both, because the twin stored in the other row is a
+ * different candidate); every component with a key hooks under the component at the other end of
+ * its entry, and when two components picked the same entry -- the only cycle a strict order allows
+ * -- the smaller root id stays root and the entry is recorded once; pointer jumping flattens the
+ * components; the number of hooks goes to the host, and the loop ends when at most one component
+ * hooked (at most that many can still grow).  A row whose entries are all inside one component is
+ * flagged and costs one byte from then on (GRX_MST_ROW_FLAGS=0 walks every row every round); rows
+ * above GRX_MST_BIG_ROW entries (default 4096) are cut into segments for whole workgroups.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels alone, batch
+ * by batch, when collect_kernel_time is set), advance_launches (kernel launches), iterations (the
+ * Boruvka rounds: defined by the schedule, <= ceil(log2 V) + 1, 0 for a graph without entries),
+ * vertices_reached (V - components = the count), edges_traversed = edges_expanded (row entries read
+ * by the minimum-search kernels, summed over rounds).  The call runs on the caller's CSR as given,
+ * builds and uses no hot-first copy, leaves nothing on the handle and releases its workspace when it
+ * returns. */
+int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int64_t* h_count, double* h_weight,
+            int32_t* d_component, const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)

@@ -31,6 +31,9 @@
  * CUs change these words while the kernel runs, and a plain load may be answered by the CU's L1 for
  * ever, or be hoisted out of the loop.  A stale value costs another trip; the compare-and-swap
  * decides.
+ *
+ * The kernels are `inline`: mst_kernels.hxx includes this file for its helpers, so two translation
+ * units see them.
  */
 #pragma once
 
@@ -92,12 +95,12 @@ __device__ __forceinline__ unsigned long long cc_block_sum(unsigned long long x,
   return total;
 }
 
-__global__ void __launch_bounds__(CC_BLOCK) cc_init_kernel(int32_t* parent, int32_t n) {
+inline __global__ void __launch_bounds__(CC_BLOCK) cc_init_kernel(int32_t* parent, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * CC_BLOCK)
     parent[v] = (int32_t)v;
 }
 
-__global__ void __launch_bounds__(CC_BLOCK)
+inline __global__ void __launch_bounds__(CC_BLOCK)
     cc_sample_kernel(const int32_t* ap, const int32_t* aj, int32_t* parent, int32_t n, int32_t r, cc_counters_t* ctr) {
   __shared__ unsigned long long s_wave[CC_BLOCK / wave_size];
   unsigned long long read = 0;
@@ -114,7 +117,7 @@ __global__ void __launch_bounds__(CC_BLOCK)
 }
 
 template <bool COUNT>
-__global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* parent, int32_t n, cc_counters_t* ctr) {
+inline __global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* parent, int32_t n, cc_counters_t* ctr) {
   __shared__ unsigned long long s_wave[CC_BLOCK / wave_size];
   unsigned long long roots = 0;
   const int lane = lane_id();
@@ -150,7 +153,7 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* parent, 
 
 /// The most frequent parent among CC_SAMPLES fixed positions (no random numbers: the answer does not
 /// depend on the pick, only the work does).  Runs after a compress: the values are roots.
-__global__ void __launch_bounds__(CC_SAMPLES) cc_pick_kernel(const int32_t* parent, int32_t n, cc_counters_t* ctr) {
+inline __global__ void __launch_bounds__(CC_SAMPLES) cc_pick_kernel(const int32_t* parent, int32_t n, cc_counters_t* ctr) {
   __shared__ int32_t s_value[CC_SAMPLES];
   __shared__ unsigned long long s_best;
   const int tid = threadIdx.x;
@@ -185,7 +188,7 @@ __device__ __forceinline__ int cc_owner(const int32_t* pre, int cnt, int32_t t) 
 
 /// `use_giant`: the picked parent is read from the counters (the pick ran in this batch of launches);
 /// otherwise no row is left out.
-__global__ void __launch_bounds__(CC_BLOCK)
+inline __global__ void __launch_bounds__(CC_BLOCK)
     cc_remainder_kernel(const int32_t* ap, const int32_t* aj, int32_t* parent, int32_t n, int32_t first, int use_giant,
                         int32_t big_row, int2* big, cc_counters_t* ctr) {
   __shared__ int32_t s_pre[CC_BLOCK], s_base[CC_BLOCK], s_wave[CC_BLOCK / wave_size + 1];
@@ -229,7 +232,7 @@ __global__ void __launch_bounds__(CC_BLOCK)
 
 /// The segments on the big list, one workgroup each: the part of a segment between 16-byte
 /// boundaries four entries per thread, its ends one entry per thread.
-__global__ void __launch_bounds__(CC_BLOCK)
+inline __global__ void __launch_bounds__(CC_BLOCK)
     cc_big_kernel(const int32_t* ap, const int32_t* aj, int32_t* parent, int32_t first, const int2* big,
                   const cc_counters_t* ctr) {
   const int32_t items = ctr->big_n;  // written by the remainder kernel before this one; constant here
@@ -258,7 +261,7 @@ __global__ void __launch_bounds__(CC_BLOCK)
 }
 
 /// Copy the counters to the host's mirror and stamp the hand-off: the last kernel of a call.
-__global__ void cc_publish_kernel(const cc_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
+inline __global__ void cc_publish_kernel(const cc_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
                                   unsigned long long sequence) {
   if (threadIdx.x == 0) {
     mirror[CC_EDGES] = ctr->edges;
