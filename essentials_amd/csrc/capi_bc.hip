@@ -1,6 +1,6 @@
 /** @file capi_bc.hip  grx_bc == gunrock::bc::run summed over a list of sources (reference
  * algorithms/bc.hxx), deterministic: the sweeps pull (hip/kernels/bc_kernels.hxx). */
-#include "capi_internal.hxx"
+#include "capi_batch.hxx"
 #include "clients.hxx"
 
 #include <gunrock/hip/kernels/bc_kernels.hxx>
@@ -36,12 +36,6 @@ struct chunk_count_t {
     return k::bc_chunks_of(in_ap[v + 1] - in_ap[v], ap[v + 1] - ap[v]);
   }
 };
-
-unsigned grid_for(std::size_t items, std::size_t per_block, gcuda::standard_context_t& ctx) {
-  const std::size_t want = (items + per_block - 1) / per_block;
-  const std::size_t most = (std::size_t)ctx.compute_units() * 8;
-  return (unsigned)std::max<std::size_t>(1, std::min(want, most));
-}
 
 }  // namespace
 
@@ -104,14 +98,8 @@ extern "C" int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources
       hip::device_array_t<int32_t> owner(max_chunks);
       float* bc = renumbered ? work_bc.data() : d_bc;
 
-      hipEvent_t start, stop;
-      GRX_HIP_CHECK(hipEventCreate(&start));
-      GRX_HIP_CHECK(hipEventCreate(&stop));
-      std::unique_ptr<std::remove_pointer_t<hipEvent_t>, void (*)(hipEvent_t)> own_start(
-          start, [](hipEvent_t e) { (void)hipEventDestroy(e); });
-      std::unique_ptr<std::remove_pointer_t<hipEvent_t>, void (*)(hipEvent_t)> own_stop(
-          stop, [](hipEvent_t e) { (void)hipEventDestroy(e); });
-      GRX_HIP_CHECK(hipEventRecord(start, s));
+      call_clock_t clock(s, false);
+      clock.start();
       if (n)
         GRX_HIP_CHECK(hipMemsetAsync(bc, 0, (std::size_t)n * sizeof(float), s));
 
@@ -246,12 +234,9 @@ extern "C" int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources
         hip::for_each_index((std::size_t)n, [from, rank_of, out] __device__(std::size_t v) { out[v] = from[rank_of[v]]; },
                             s);
       }
-      GRX_HIP_CHECK(hipEventRecord(stop, s));
-      GRX_HIP_CHECK(hipEventSynchronize(stop));
+      clock.stop_and_wait();
       if (stats) {
-        float ms = 0;
-        GRX_HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-        stats->elapsed_ms = ms;
+        stats->elapsed_ms = clock.elapsed_ms();
         stats->iterations = (int32_t)std::min<long long>(levels_total, INT32_MAX);
         stats->vertices_reached = reached_total;
         stats->edges_traversed = edges_total;

@@ -2,28 +2,15 @@
  * -- lock-free union-find on the output array, neighbour rounds, and a remainder pass that leaves the
  * rows of the picked component unread when the CSR is known to be symmetric
  * (hip/kernels/cc_kernels.hxx).  No reference counterpart.  One batch of launches, one hand-off. */
-#include "capi_internal.hxx"
+#include "capi_batch.hxx"
 
 #include <gunrock/hip/kernels/cc_kernels.hxx>
 
-#include <cstdlib>
 #include <cstring>
 
 using namespace essentials_amd;
 
-namespace {
-
 namespace k = gunrock::hip::kernels;
-
-/// Test hooks: GRX_CC_SAMPLE_ROUNDS (neighbour rounds; 0 = hook every entry, leave no row out) and
-/// GRX_CC_BIG_ROW (rows with more entries left than this are cut into segments for whole workgroups).
-long long env_or(const char* name, long long fallback, long long lo, long long hi) {
-  if (const char* e = std::getenv(name))
-    return std::max(lo, std::min(hi, std::atoll(e)));
-  return fallback;
-}
-
-}  // namespace
 
 extern "C" int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_components,
                       const grx_options* opt, grx_stats* stats) {
@@ -47,25 +34,16 @@ extern "C" int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, in
     auto& sc = ctx->single();
     const hipStream_t s = sc.stream();
 
+    // test hooks: the neighbour rounds (0 = hook every entry, leave no row out), and the entries
+    // left above which a row is cut into segments for whole workgroups
     const int32_t rounds = (int32_t)env_or("GRX_CC_SAMPLE_ROUNDS", k::CC_SAMPLE_ROUNDS, 0, k::CC_MAX_ROUNDS);
     const int32_t big_row = (int32_t)env_or("GRX_CC_BIG_ROW", k::CC_BIG_ROW, 1, INT32_MAX);
     // a row of the picked component may stay unread only when its entries are stored from the other
     // end too: the handle's verdict as it stands (verifying it costs more than the whole call)
     const bool skip = rounds > 0 && !g->in_edges && g->symmetry == grx_graph_s::symmetric;
 
-    hipEvent_t start, stop, first = nullptr, last = nullptr;
-    GRX_HIP_CHECK(hipEventCreate(&start));
-    GRX_HIP_CHECK(hipEventCreate(&stop));
-    auto destroy = [](hipEvent_t e) { (void)hipEventDestroy(e); };
-    using event_owner = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, void (*)(hipEvent_t)>;
-    event_owner own_start(start, destroy), own_stop(stop, destroy), own_first(nullptr, destroy), own_last(nullptr, destroy);
-    if (timed) {  // collect_kernel_time: one event pair around the batch of launches
-      GRX_HIP_CHECK(hipEventCreate(&first));
-      own_first.reset(first);
-      GRX_HIP_CHECK(hipEventCreate(&last));
-      own_last.reset(last);
-    }
-    GRX_HIP_CHECK(hipEventRecord(start, s));
+    call_clock_t clock(s, timed);
+    clock.start();
 
     int32_t launches = 0;
     unsigned long long edges = 0, components = 0;
@@ -77,13 +55,9 @@ extern "C" int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, in
       k::cc_counters_t* ctr = counters.data();
       GRX_HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof *ctr, s));
 
-      auto& ws = sc.workspace();
-      const unsigned most = (unsigned)sc.compute_units() * 8;
-      const unsigned grid =
-          (unsigned)std::max<std::size_t>(1, std::min<std::size_t>(((std::size_t)n + k::CC_BLOCK - 1) / k::CC_BLOCK, most));
+      const unsigned grid = grid_for((std::size_t)n, k::CC_BLOCK, sc);
 
-      if (timed)
-        GRX_HIP_CHECK(hipEventRecord(first, s));
+      clock.begin_batch();
       k::cc_init_kernel<<<grid, k::CC_BLOCK, 0, s>>>(parent, n);
       ++launches;
       for (int32_t r = 0; r < rounds; ++r) {
@@ -100,31 +74,22 @@ extern "C" int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, in
       k::cc_big_kernel<<<(unsigned)sc.compute_units() * 4, k::CC_BLOCK, 0, s>>>(g->d_ap, g->d_aj, parent, rounds, big.data(),
                                                                               ctr);
       k::cc_compress_kernel<true><<<grid, k::CC_BLOCK, 0, s>>>(parent, n, ctr);
-      const unsigned long long seq = ws.next_sequence();
-      k::cc_publish_kernel<<<1, 64, 0, s>>>(ctr, ws.mirror(), (int)gcuda::workspace_t::sequence_slot, seq);
       launches += 4;
-      GRX_HIP_CHECK(hipGetLastError());
-      if (timed)
-        GRX_HIP_CHECK(hipEventRecord(last, s));
       // the one hand-off of the call
-      const unsigned long long* m = operators::advance::detail::await_counters(sc, seq);
+      const unsigned long long* m = hand_off(sc, clock, [&](unsigned long long* mirror, int slot, unsigned long long seq) {
+        k::cc_publish_kernel<<<1, 64, 0, s>>>(ctr, mirror, slot, seq);
+      });
       edges = m[k::CC_EDGES];
       components = m[k::CC_COMPONENTS];
-      GRX_HIP_CHECK(hipEventRecord(stop, s));
-      GRX_HIP_CHECK(hipEventSynchronize(stop));
+      clock.stop_and_wait();
     }
     hip::block_cache_t::instance().trim();
 
     if (h_components)
       *h_components = (int64_t)components;
     if (stats) {
-      float ms = 0;
-      GRX_HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-      stats->elapsed_ms = ms;
-      if (timed) {
-        GRX_HIP_CHECK(hipEventElapsedTime(&ms, first, last));
-        stats->advance_kernel_ms = ms;
-      }
+      stats->elapsed_ms = clock.elapsed_ms();
+      stats->advance_kernel_ms = clock.kernel_ms();
       stats->iterations = rounds + 1;
       stats->advance_launches = launches;
       stats->vertices_reached = (int64_t)n - (int64_t)components;

@@ -2,29 +2,15 @@
  * per level one seed scan, then removal rounds until the queue is empty, every row walked once
  * when its vertex leaves (hip/kernels/kcore_kernels.hxx).  Each batch of launches ends with the
  * one-workgroup kernel, which runs the small generations itself and hands the counters over. */
-#include "capi_internal.hxx"
+#include "capi_batch.hxx"
 
 #include <gunrock/hip/kernels/kcore_kernels.hxx>
 
-#include <cstdlib>
 #include <cstring>
 
 using namespace essentials_amd;
 
-namespace {
-
 namespace k = gunrock::hip::kernels;
-
-/// Test hooks: GRX_KCORE_NARROW_EDGES (entries a generation may have to stay in the one-workgroup
-/// kernel; 0 sends every generation to the wide kernel) and GRX_KCORE_BIG_ROW (rows longer than
-/// this are walked by the whole grid).
-long long env_or(const char* name, long long fallback, long long lo, long long hi) {
-  if (const char* e = std::getenv(name))
-    return std::max(lo, std::min(hi, std::atoll(e)));
-  return fallback;
-}
-
-}  // namespace
 
 extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int32_t* h_degeneracy,
                          const grx_options* opt, grx_stats* stats) {
@@ -45,43 +31,19 @@ extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int3
       *h_degeneracy = 0;
     if (n == 0)  // the empty graph: nothing to write
       return (int)GRX_OK;
-    if (g->in_edges)
-      return unsupported("grx_kcore: the graph has in-edges attached (directed); k-core decomposition "
-                         "needs a symmetric CSR");
-    if (ensure_can_pull(ctx, g) != GRX_OK)
-      return unsupported("grx_kcore: the CSR is not symmetric (directed); k-core decomposition needs a "
-                         "symmetric CSR");
+    if (int rc = require_symmetric(ctx, g, "grx_kcore", "k-core decomposition"))
+      return rc;
     auto& sc = ctx->single();
     const hipStream_t s = sc.stream();
 
+    // test hooks: the entries a generation may have to stay in the one-workgroup kernel (0 sends
+    // every generation to the wide kernel), and the row length above which the whole grid walks a row
     const unsigned long long narrow_edges =
         (unsigned long long)env_or("GRX_KCORE_NARROW_EDGES", k::KCORE_NARROW_EDGES, 0, 1ll << 30);
     const int32_t big_row = (int32_t)env_or("GRX_KCORE_BIG_ROW", k::KCORE_BIG_ROW, 1, INT32_MAX);
 
-    hipEvent_t start, stop;
-    GRX_HIP_CHECK(hipEventCreate(&start));
-    GRX_HIP_CHECK(hipEventCreate(&stop));
-    auto destroy = [](hipEvent_t e) { (void)hipEventDestroy(e); };
-    std::unique_ptr<std::remove_pointer_t<hipEvent_t>, void (*)(hipEvent_t)> own_start(start, destroy),
-        own_stop(stop, destroy);
-    // collect_kernel_time: one event pair around every batch of launches
-    std::vector<hipEvent_t> marks;
-    struct marks_guard {
-      std::vector<hipEvent_t>& m;
-      ~marks_guard() {
-        for (hipEvent_t e : m)
-          (void)hipEventDestroy(e);
-      }
-    } own_marks{marks};
-    auto mark = [&] {
-      if (!timed)
-        return;
-      hipEvent_t e;
-      GRX_HIP_CHECK(hipEventCreate(&e));
-      marks.push_back(e);
-      GRX_HIP_CHECK(hipEventRecord(e, s));
-    };
-    GRX_HIP_CHECK(hipEventRecord(start, s));
+    call_clock_t clock(s, timed);
+    clock.start();
 
     int32_t degeneracy = 0, levels = 0, launches = 0;
     unsigned long long edges = 0, nonempty = 0;
@@ -95,35 +57,25 @@ extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int3
       GRX_HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof *ctr, s));
       GRX_HIP_CHECK(hipMemsetAsync(&ctr->next_k, 0xff, sizeof ctr->next_k, s));  // KCORE_NONE
 
-      auto& ws = sc.workspace();
-      const int slot = (int)gcuda::workspace_t::sequence_slot;
       const unsigned most = (unsigned)sc.compute_units() * 8;
-      const unsigned scan_grid =
-          (unsigned)std::max<std::size_t>(1, std::min<std::size_t>(((std::size_t)n + k::KCORE_BLOCK - 1) / k::KCORE_BLOCK, most));
-      // the hand-off that ends a batch: wait for the last kernel's stamp, read the mirror
+      const unsigned scan_grid = grid_for((std::size_t)n, k::KCORE_BLOCK, sc);
+      // the hand-off that ends a batch is the narrow kernel's last act
       unsigned long long* m = nullptr;
-      auto await = [&](unsigned long long seq) {
-        GRX_HIP_CHECK(hipGetLastError());
-        mark();
-        m = operators::advance::detail::await_counters(sc, seq);
-      };
       auto narrow = [&](int32_t level) {
-        const unsigned long long seq = ws.next_sequence();
-        k::kcore_narrow_kernel<<<1, k::KCORE_NARROW_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(), core, queue.data(), level,
-                                                                  k::KCORE_NARROW_BLOCK, narrow_edges, ctr, ws.mirror(),
-                                                                  slot, seq);
+        m = hand_off(sc, clock, [&](unsigned long long* mirror, int slot, unsigned long long seq) {
+          k::kcore_narrow_kernel<<<1, k::KCORE_NARROW_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(), core, queue.data(),
+                                                                    level, k::KCORE_NARROW_BLOCK, narrow_edges, ctr,
+                                                                    mirror, slot, seq);
+        });
         ++launches;
-        await(seq);
       };
 
-      mark();
+      clock.begin_batch();
       k::kcore_init_kernel<<<scan_grid, k::KCORE_BLOCK, 0, s>>>(g->d_ap, n, deg.data(), core, ctr);
-      {
-        const unsigned long long seq = ws.next_sequence();
-        k::kcore_publish_kernel<<<1, 64, 0, s>>>(ctr, ws.mirror(), slot, seq);
-        launches += 2;
-        await(seq);
-      }
+      m = hand_off(sc, clock, [&](unsigned long long* mirror, int slot, unsigned long long seq) {
+        k::kcore_publish_kernel<<<1, 64, 0, s>>>(ctr, mirror, slot, seq);
+      });
+      launches += 2;
       const bool has_big = m[k::KC_MAX_ROW] > (unsigned long long)big_row;
       nonempty = m[k::KC_NONEMPTY];
       int32_t k_prev = 0;
@@ -131,7 +83,7 @@ extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int3
       while ((unsigned)m[k::KC_NEXT_K] != k::KCORE_NONE) {
         const int32_t level = (int32_t)m[k::KC_NEXT_K];
         const unsigned long long queued_before = m[k::KC_TAIL];
-        mark();
+        clock.begin_batch();
         k::kcore_seed_kernel<<<scan_grid, k::KCORE_BLOCK, 0, s>>>(g->d_ap, deg.data(), n, k_prev, level, queue.data(), ctr);
         ++launches;
         narrow(level);
@@ -140,8 +92,8 @@ extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int3
           const int32_t head = (int32_t)m[k::KC_HEAD], tail = (int32_t)m[k::KC_TAIL];
           const int32_t count = tail - head;
           const int32_t chunk = std::max(1, std::min<int32_t>(k::KCORE_BLOCK, (count + (int32_t)most - 1) / (int32_t)most));
-          const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)count + chunk - 1) / chunk, (int64_t)most);
-          mark();
+          const unsigned grid = grid_for((std::size_t)count, (std::size_t)chunk, sc);
+          clock.begin_batch();
           k::kcore_wide_kernel<<<grid, k::KCORE_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(), core, queue.data(), head, tail,
                                                               chunk, level, big_row, big.data(), ctr);
           ++launches;
@@ -161,21 +113,15 @@ extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int3
         }
       }
       edges = m[k::KC_EDGES];
-      GRX_HIP_CHECK(hipEventRecord(stop, s));
-      GRX_HIP_CHECK(hipEventSynchronize(stop));
+      clock.stop_and_wait();
     }
     hip::block_cache_t::instance().trim();
 
     if (h_degeneracy)
       *h_degeneracy = degeneracy;
     if (stats) {
-      float ms = 0;
-      GRX_HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-      stats->elapsed_ms = ms;
-      for (std::size_t i = 0; i + 1 < marks.size(); i += 2) {
-        GRX_HIP_CHECK(hipEventElapsedTime(&ms, marks[i], marks[i + 1]));
-        stats->advance_kernel_ms += ms;
-      }
+      stats->elapsed_ms = clock.elapsed_ms();
+      stats->advance_kernel_ms = clock.kernel_ms();
       stats->iterations = levels;
       stats->advance_launches = launches;
       stats->vertices_reached = (int64_t)nonempty;

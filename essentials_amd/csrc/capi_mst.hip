@@ -3,11 +3,10 @@
  * (ordered_bits(weight), position) (hip/kernels/mst_kernels.hxx).  The reference's mst.hxx returns one
  * order-dependent float on connected graphs only; this returns the entries, an exact count, a
  * reproducible float64 weight and the component labels, on any graph.  One hand-off per round + one. */
-#include "capi_internal.hxx"
+#include "capi_batch.hxx"
 
 #include <gunrock/hip/kernels/mst_kernels.hxx>
 
-#include <cstdlib>
 #include <cstring>
 
 using namespace essentials_amd;
@@ -15,15 +14,6 @@ using namespace essentials_amd;
 namespace {
 
 namespace k = gunrock::hip::kernels;
-
-/// Test hooks: GRX_MST_BIG_ROW (rows with more entries than this are cut into segments for whole
-/// workgroups) and GRX_MST_ROW_FLAGS (1: a row whose entries are all inside one component is flagged
-/// and not walked again; 0: every row is walked in every round).
-long long env_or(const char* name, long long fallback, long long lo, long long hi) {
-  if (const char* e = std::getenv(name))
-    return std::max(lo, std::min(hi, std::atoll(e)));
-  return fallback;
-}
 
 /// ceil(log2(x)) for x >= 1.
 int ceil_log2(unsigned long long x) {
@@ -59,27 +49,18 @@ extern "C" int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int
     auto& sc = ctx->single();
     const hipStream_t s = sc.stream();
 
+    // test hooks: the entries above which a row is cut into segments for whole workgroups, and the
+    // row flags (1: a row whose entries are all inside one component is flagged and not walked
+    // again; 0: every row is walked in every round)
     const int32_t big_row = (int32_t)env_or("GRX_MST_BIG_ROW", k::MST_BIG_ROW, 1, INT32_MAX);
     const int use_flags = (int)env_or("GRX_MST_ROW_FLAGS", 1, 0, 1);
 
-    hipEvent_t start, stop, first = nullptr, last = nullptr;
-    GRX_HIP_CHECK(hipEventCreate(&start));
-    GRX_HIP_CHECK(hipEventCreate(&stop));
-    auto destroy = [](hipEvent_t e) { (void)hipEventDestroy(e); };
-    using event_owner = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, void (*)(hipEvent_t)>;
-    event_owner own_start(start, destroy), own_stop(stop, destroy), own_first(nullptr, destroy), own_last(nullptr, destroy);
-    if (timed) {  // collect_kernel_time: one event pair around each batch of launches
-      GRX_HIP_CHECK(hipEventCreate(&first));
-      own_first.reset(first);
-      GRX_HIP_CHECK(hipEventCreate(&last));
-      own_last.reset(last);
-    }
-    GRX_HIP_CHECK(hipEventRecord(start, s));
+    call_clock_t clock(s, timed);
+    clock.start();
 
     int32_t launches = 0, rounds = 0;
     unsigned long long edges = 0, count = 0;
     double weight = 0.0;
-    float kernel_ms = 0;
     {
       const int64_t nnz = g->nnz;
       const int64_t words = (nnz + 31) / 32, tiles = (words + k::MST_BLOCK - 1) / k::MST_BLOCK;
@@ -96,35 +77,16 @@ extern "C" int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int
       GRX_HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof *ctr, s));
       GRX_HIP_CHECK(hipMemsetAsync(chosen.data(), 0, (std::size_t)std::max<int64_t>(words, 1) * sizeof(unsigned int), s));
 
-      auto& ws = sc.workspace();
-      const unsigned most = (unsigned)sc.compute_units() * 8;
-      const unsigned grid =
-          (unsigned)std::max<std::size_t>(1, std::min<std::size_t>(((std::size_t)n + k::MST_BLOCK - 1) / k::MST_BLOCK, most));
-      const unsigned tile_grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)most));
+      const unsigned grid = grid_for((std::size_t)n, k::MST_BLOCK, sc);
+      const unsigned tile_grid = grid_for((std::size_t)tiles, 1, sc);
 
-      auto begin = [&] {
-        if (timed)
-          GRX_HIP_CHECK(hipEventRecord(first, s));
-      };
       // the hand-off that ends a batch of launches
-      auto hand_off = [&]() -> const unsigned long long* {
-        const unsigned long long seq = ws.next_sequence();
-        k::mst_publish_kernel<<<1, 64, 0, s>>>(ctr, ws.mirror(), (int)gcuda::workspace_t::sequence_slot, seq);
+      auto publish = [&](unsigned long long* mirror, int slot, unsigned long long seq) {
+        k::mst_publish_kernel<<<1, 64, 0, s>>>(ctr, mirror, slot, seq);
         ++launches;
-        GRX_HIP_CHECK(hipGetLastError());
-        if (timed)
-          GRX_HIP_CHECK(hipEventRecord(last, s));
-        const unsigned long long* m = operators::advance::detail::await_counters(sc, seq);
-        if (timed) {
-          float ms = 0;
-          GRX_HIP_CHECK(hipEventSynchronize(last));
-          GRX_HIP_CHECK(hipEventElapsedTime(&ms, first, last));
-          kernel_ms += ms;
-        }
-        return m;
       };
 
-      begin();
+      clock.begin_batch();
       k::mst_init_kernel<<<grid, k::MST_BLOCK, 0, s>>>(comp.data(), best.data(), done.data(), n);
       ++launches;
       // Components that can still grow: one that did not merge in a round has no outgoing entry and
@@ -133,7 +95,7 @@ extern "C" int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int
       unsigned long long live = (unsigned long long)n;
       while (nnz > 0 && live > 1) {
         if (rounds)
-          begin();
+          clock.begin_batch();
         k::mst_search_kernel<<<grid, k::MST_BLOCK, 0, s>>>(g->d_ap, g->d_aj, g->d_ax, comp.data(), best.data(), done.data(), n,
                                                          use_flags, big_row, big.data(), ctr);
         k::mst_big_kernel<<<(unsigned)sc.compute_units() * 4, k::MST_BLOCK, 0, s>>>(g->d_ap, g->d_aj, g->d_ax, comp.data(),
@@ -147,14 +109,14 @@ extern "C" int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int
         k::mst_flatten_kernel<<<grid, k::MST_BLOCK, 0, s>>>(comp.data(), link.data(), best.data(), n);
         launches += 4 + jumps;
         ++rounds;
-        const unsigned long long* m = hand_off();
+        const unsigned long long* m = hand_off(sc, clock, publish);
         edges = m[k::MST_EDGES];
         live = m[k::MST_HOOKED];
       }
 
       // the last batch: labels, the chosen positions in ascending order, their weights' sum
       if (rounds)
-        begin();
+        clock.begin_batch();
       if (d_component) {
         k::mst_minid_init_kernel<<<grid, k::MST_BLOCK, 0, s>>>(link.data(), n);
         k::mst_minid_kernel<<<grid, k::MST_BLOCK, 0, s>>>(comp.data(), link.data(), n);
@@ -169,12 +131,11 @@ extern "C" int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int
         k::mst_sum_kernel<<<1, k::MST_SCAN_BLOCK, 0, s>>>(tile_sum.data(), tiles, ctr);
         launches += 4;
       }
-      const unsigned long long* m = hand_off();
+      const unsigned long long* m = hand_off(sc, clock, publish);
       count = m[k::MST_COUNT];
       const long long bits = (long long)m[k::MST_WEIGHT];
       std::memcpy(&weight, &bits, sizeof weight);
-      GRX_HIP_CHECK(hipEventRecord(stop, s));
-      GRX_HIP_CHECK(hipEventSynchronize(stop));
+      clock.stop_and_wait();
     }
     hip::block_cache_t::instance().trim();
 
@@ -183,11 +144,8 @@ extern "C" int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int
     if (h_weight)
       *h_weight = weight;
     if (stats) {
-      float ms = 0;
-      GRX_HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-      stats->elapsed_ms = ms;
-      if (timed)
-        stats->advance_kernel_ms = kernel_ms;
+      stats->elapsed_ms = clock.elapsed_ms();
+      stats->advance_kernel_ms = clock.kernel_ms();
       stats->iterations = rounds;
       stats->advance_launches = launches;
       stats->vertices_reached = (int64_t)count;

@@ -1,11 +1,10 @@
 /** @file capi_tc.hip  grx_tc == gunrock::tc::run (reference algorithms/tc.hxx) on the simple
  * undirected graph under a symmetric CSR: a degree-oriented, sorted, deduplicated copy L is built
  * per call and every triangle is found once, at its lowest-ranked vertex (hip/kernels/tc_kernels.hxx). */
-#include "capi_internal.hxx"
+#include "capi_batch.hxx"
 
 #include <gunrock/hip/kernels/tc_kernels.hxx>
 
-#include <cstdlib>
 #include <cstring>
 
 using namespace essentials_amd;
@@ -27,12 +26,6 @@ struct class_key_t {
   int32_t b[4];
   __host__ __device__ unsigned operator()(int32_t u) const { return k::tc_class_of(lap[u + 1] - lap[u], b); }
 };
-
-unsigned grid_for(std::size_t items, std::size_t per_block, gcuda::standard_context_t& ctx) {
-  const std::size_t want = (items + per_block - 1) / per_block;
-  const std::size_t most = (std::size_t)ctx.compute_units() * 8;
-  return (unsigned)std::max<std::size_t>(1, std::min(want, most));
-}
 
 /// Exclusive scan of count[0, n) into out[0, n] (out[n] = the sum).
 void scan_counts(const int32_t* count, int32_t n, int32_t* out, hip::device_array_t<unsigned char>& temp,
@@ -56,14 +49,8 @@ extern "C" int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triang
     return invalid("grx_tc: the graph is not square (n_rows != n_cols)");
   const bool timed = opt && opt->collect_kernel_time;
   return guarded([&] {
-    // undirected input only: an attached transpose marks the graph directed, and a graph nobody
-    // has vouched for is verified once (ensure_can_pull returns OK when in-edges are attached)
-    if (g->in_edges)
-      return unsupported("grx_tc: the graph has in-edges attached (directed); triangle counting needs "
-                         "a symmetric CSR");
-    if (ensure_can_pull(ctx, g) != GRX_OK)
-      return unsupported("grx_tc: the CSR is not symmetric (directed); triangle counting needs a "
-                         "symmetric CSR");
+    if (int rc = require_symmetric(ctx, g, "grx_tc", "triangle counting"))
+      return rc;
     auto& sc = ctx->single();
     const hipStream_t s = sc.stream();
     const int32_t n = g->n_rows;
@@ -78,19 +65,11 @@ extern "C" int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triang
       GRX_HIP_CHECK(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
       const int fit = (max_lds - 1024) / k::TC_SLOT_BYTES;  // the static part stays below 1 KB
       lds_ids = std::min(lds_ids, fit);
-      if (const char* e = std::getenv("GRX_TC_LDS_IDS"))  // test hook: lower the capacity
-        lds_ids = std::max(1, std::min(lds_ids, std::atoi(e)));
+      lds_ids = (int32_t)env_or("GRX_TC_LDS_IDS", lds_ids, 1, lds_ids);  // test hook: lower the capacity
     }
 
-    hipEvent_t start, stop, k0, k1;
-    GRX_HIP_CHECK(hipEventCreate(&start));
-    GRX_HIP_CHECK(hipEventCreate(&stop));
-    GRX_HIP_CHECK(hipEventCreate(&k0));
-    GRX_HIP_CHECK(hipEventCreate(&k1));
-    auto destroy = [](hipEvent_t e) { (void)hipEventDestroy(e); };
-    std::unique_ptr<std::remove_pointer_t<hipEvent_t>, void (*)(hipEvent_t)> own_start(start, destroy),
-        own_stop(stop, destroy), own_k0(k0, destroy), own_k1(k1, destroy);
-    GRX_HIP_CHECK(hipEventRecord(start, s));
+    call_clock_t clock(s, timed);
+    clock.start();
     if (d_vertex_triangles && n)
       GRX_HIP_CHECK(hipMemsetAsync(d_vertex_triangles, 0, (std::size_t)n * sizeof(int64_t), s));
 
@@ -177,8 +156,7 @@ extern "C" int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triang
       GRX_HIP_CHECK(hipMemsetAsync(totals.data(), 0, sizeof h_totals, s));
       auto* counts = reinterpret_cast<unsigned long long*>(d_vertex_triangles);
       hip::device_array_t<int32_t> ws(rows_of(5) ? 3 * (std::size_t)m : 0);
-      if (timed)
-        GRX_HIP_CHECK(hipEventRecord(k0, s));
+      clock.begin_batch();
       if (int32_t r = rows_of(5)) {
         k::tc_block_kernel<false><<<grid_for((std::size_t)r, 1, sc), k::TC_BLOCK, 0, s>>>(
             lap.data(), laj.data(), rows_at[5], r, 0, ws.data(), m, counts, totals.data());
@@ -210,11 +188,9 @@ extern "C" int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triang
                                           s>>>(lap.data(), laj.data(), rows_at[1], r, counts, totals.data());
         GRX_HIP_CHECK(hipGetLastError());
       }
-      if (timed)
-        GRX_HIP_CHECK(hipEventRecord(k1, s));
+      clock.end_batch();
       GRX_HIP_CHECK(hipMemcpyAsync(h_totals, totals.data(), sizeof h_totals, hipMemcpyDeviceToHost, s));
-      GRX_HIP_CHECK(hipEventRecord(stop, s));
-      GRX_HIP_CHECK(hipEventSynchronize(stop));
+      clock.stop_and_wait();
     }
     // the key buffers are large and of no use to the operators: do not park them
     hip::block_cache_t::instance().trim();
@@ -222,13 +198,8 @@ extern "C" int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triang
     if (h_triangles)
       *h_triangles = (uint64_t)h_totals[0];
     if (stats) {
-      float ms = 0;
-      GRX_HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
-      stats->elapsed_ms = ms;
-      if (timed) {
-        GRX_HIP_CHECK(hipEventElapsedTime(&ms, k0, k1));
-        stats->advance_kernel_ms = ms;
-      }
+      stats->elapsed_ms = clock.elapsed_ms();
+      stats->advance_kernel_ms = clock.kernel_ms();
       stats->iterations = 1;
       stats->edges_traversed = (int64_t)m;
       stats->edges_expanded = (int64_t)h_totals[1];

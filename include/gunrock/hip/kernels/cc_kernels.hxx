@@ -19,8 +19,7 @@
  *                        leaves the most frequent value (ties: the smaller) in the counters.
  *   cc_remainder_kernel  a chunk of CC_BLOCK consecutive vertices per workgroup: the entries from
  *                        position `first` on of every vertex whose parent is not the picked one,
- *                        flattened over the workgroup's threads (prefix of the lengths in LDS,
- *                        owner by binary search: consecutive threads read consecutive entries).
+ *                        flattened over the workgroup's threads (flat_walk, row_walk.hxx).
  *                        Rows with more than `big_row` entries left go to a list, cut into
  *                        segments of CC_BIG_SEGMENT entries ...
  *   cc_big_kernel        ... which the grid walks a workgroup per segment, 16 bytes of the row per
@@ -31,13 +30,10 @@
  * CUs change these words while the kernel runs, and a plain load may be answered by the CU's L1 for
  * ever, or be hoisted out of the loop.  A stale value costs another trip; the compare-and-swap
  * decides.
- *
- * The kernels are `inline`: mst_kernels.hxx includes this file for its helpers, so two translation
- * units see them.
  */
 #pragma once
 
-#include <gunrock/hip/primitives.hxx>
+#include <gunrock/hip/kernels/row_walk.hxx>
 
 namespace gunrock {
 namespace hip {
@@ -61,46 +57,28 @@ struct cc_counters_t {
 /// What the host reads at the hand-off (words of the pinned mirror).
 enum { CC_EDGES = 0, CC_COMPONENTS, CC_GIANT, CC_WORDS };
 
-__device__ __forceinline__ int32_t cc_load(const int32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 /// Join the trees of u and v: the larger root is hooked under the smaller.  Every trip moves up a
 /// tree or ends, and trees are finite (parent[x] < x below a root).
 __device__ __forceinline__ void cc_link(int32_t* parent, int32_t u, int32_t v) {
-  int32_t p1 = cc_load(parent + u), p2 = cc_load(parent + v);
+  int32_t p1 = load_relaxed(parent + u), p2 = load_relaxed(parent + v);
   while (p1 != p2) {
     const int32_t high = p1 > p2 ? p1 : p2, low = p1 > p2 ? p2 : p1;
-    const int32_t p_high = cc_load(parent + high);
+    const int32_t p_high = load_relaxed(parent + high);
     if (p_high == low)
       break;
     if (p_high == high && atomicCAS(parent + high, high, low) == high)
       break;
-    p1 = cc_load(parent + cc_load(parent + high));
-    p2 = cc_load(parent + low);
+    p1 = load_relaxed(parent + load_relaxed(parent + high));
+    p2 = load_relaxed(parent + low);
   }
 }
 
-/// Sum over the workgroup, valid in thread 0.  `s_wave`: BLOCK / 64 words of LDS.  One barrier.
-template <int BLOCK>
-__device__ __forceinline__ unsigned long long cc_block_sum(unsigned long long x, unsigned long long* s_wave) {
-  x = wave_sum(x);
-  if (lane_id() == 0)
-    s_wave[threadIdx.x / wave_size] = x;
-  __syncthreads();
-  unsigned long long total = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < BLOCK / wave_size; ++w)
-      total += s_wave[w];
-  return total;
-}
-
-inline __global__ void __launch_bounds__(CC_BLOCK) cc_init_kernel(int32_t* parent, int32_t n) {
+__global__ void __launch_bounds__(CC_BLOCK) cc_init_kernel(int32_t* parent, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)CC_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * CC_BLOCK)
     parent[v] = (int32_t)v;
 }
 
-inline __global__ void __launch_bounds__(CC_BLOCK)
+__global__ void __launch_bounds__(CC_BLOCK)
     cc_sample_kernel(const int32_t* ap, const int32_t* aj, int32_t* parent, int32_t n, int32_t r, cc_counters_t* ctr) {
   __shared__ unsigned long long s_wave[CC_BLOCK / wave_size];
   unsigned long long read = 0;
@@ -111,13 +89,13 @@ inline __global__ void __launch_bounds__(CC_BLOCK)
       ++read;
     }
   }
-  read = cc_block_sum<CC_BLOCK>(read, s_wave);
+  read = block_sum<CC_BLOCK>(read, s_wave);
   if (threadIdx.x == 0 && read)
     atomicAdd(&ctr->edges, read);
 }
 
 template <bool COUNT>
-inline __global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* parent, int32_t n, cc_counters_t* ctr) {
+__global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* parent, int32_t n, cc_counters_t* ctr) {
   __shared__ unsigned long long s_wave[CC_BLOCK / wave_size];
   unsigned long long roots = 0;
   const int lane = lane_id();
@@ -128,14 +106,14 @@ inline __global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* p
     bool root = false;
     if (v < n) {
       // a racing compress writes an ancestor either way; the chain above p only gets shorter
-      int32_t p = cc_load(parent + v), pp = cc_load(parent + p);
+      int32_t p = load_relaxed(parent + v), pp = load_relaxed(parent + p);
       const int32_t was = p;
       while (p != pp) {
         p = pp;
-        pp = cc_load(parent + p);
+        pp = load_relaxed(parent + p);
       }
       if (p != was)
-        __hip_atomic_store(parent + v, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        store_relaxed(parent + v, p);
       root = p == (int32_t)v;
     }
     if (COUNT) {
@@ -145,7 +123,7 @@ inline __global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* p
     }
   }
   if (COUNT) {
-    roots = cc_block_sum<CC_BLOCK>(roots, s_wave);
+    roots = block_sum<CC_BLOCK>(roots, s_wave);
     if (threadIdx.x == 0 && roots)
       atomicAdd(&ctr->components, roots);
   }
@@ -153,7 +131,7 @@ inline __global__ void __launch_bounds__(CC_BLOCK) cc_compress_kernel(int32_t* p
 
 /// The most frequent parent among CC_SAMPLES fixed positions (no random numbers: the answer does not
 /// depend on the pick, only the work does).  Runs after a compress: the values are roots.
-inline __global__ void __launch_bounds__(CC_SAMPLES) cc_pick_kernel(const int32_t* parent, int32_t n, cc_counters_t* ctr) {
+__global__ void __launch_bounds__(CC_SAMPLES) cc_pick_kernel(const int32_t* parent, int32_t n, cc_counters_t* ctr) {
   __shared__ int32_t s_value[CC_SAMPLES];
   __shared__ unsigned long long s_best;
   const int tid = threadIdx.x;
@@ -173,22 +151,9 @@ inline __global__ void __launch_bounds__(CC_SAMPLES) cc_pick_kernel(const int32_
     ctr->giant = (int32_t)(0x7fffffffu - (unsigned)(s_best & 0xffffffffu));
 }
 
-/// Smallest i in [0, cnt) with pre[i] > t (pre inclusive and non-decreasing, t < pre[cnt - 1]).
-__device__ __forceinline__ int cc_owner(const int32_t* pre, int cnt, int32_t t) {
-  int lo = 0, hi = cnt - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (pre[mid] > t)
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  return lo;
-}
-
 /// `use_giant`: the picked parent is read from the counters (the pick ran in this batch of launches);
 /// otherwise no row is left out.
-inline __global__ void __launch_bounds__(CC_BLOCK)
+__global__ void __launch_bounds__(CC_BLOCK)
     cc_remainder_kernel(const int32_t* ap, const int32_t* aj, int32_t* parent, int32_t n, int32_t first, int use_giant,
                         int32_t big_row, int2* big, cc_counters_t* ctr) {
   __shared__ int32_t s_pre[CC_BLOCK], s_base[CC_BLOCK], s_wave[CC_BLOCK / wave_size + 1];
@@ -199,40 +164,28 @@ inline __global__ void __launch_bounds__(CC_BLOCK)
   for (int64_t a = blockIdx.x * (int64_t)CC_BLOCK; a < n; a += (int64_t)gridDim.x * CC_BLOCK) {
     const int64_t v = a + tid;
     int32_t lo = 0, d = 0;
-    if (v < n && cc_load(parent + v) != giant) {
+    if (v < n && load_relaxed(parent + v) != giant) {
       lo = ap[v] + first;
       d = max(ap[v + 1] - lo, 0);
       if (d > big_row) {
-        const int32_t segments = (d + CC_BIG_SEGMENT - 1) / CC_BIG_SEGMENT;
-        const int32_t at = atomicAdd(&ctr->big_n, segments);
-        for (int32_t k = 0; k < segments; ++k)
-          big[at + k] = make_int2((int32_t)v, k);
+        push_big_segments<CC_BIG_SEGMENT>(&ctr->big_n, big, (int32_t)v, d);
         read += (unsigned long long)d;
         d = 0;
       }
     }
-    int32_t P = 0;
-    const int32_t excl = block_exclusive_sum<CC_BLOCK>(d, P, s_wave);
-    if (P == 0)  // uniform: the whole chunk is in the picked component, or has nothing left
-      continue;
-    s_pre[tid] = excl + d;
-    s_base[tid] = lo - excl;
-    __syncthreads();
-    for (int32_t t = tid; t < P; t += CC_BLOCK) {
-      const int o = cc_owner(s_pre, CC_BLOCK, t);
-      cc_link(parent, (int32_t)a + o, aj[s_base[o] + t]);
-    }
+    // P == 0: the whole chunk is in the picked component, or has nothing left
+    const int32_t P = flat_walk<CC_BLOCK>(d, lo, s_pre, s_base, s_wave,
+                                          [&](int o, int32_t e) { cc_link(parent, (int32_t)a + o, aj[e]); });
     read += (unsigned long long)(tid == 0 ? P : 0);
-    __syncthreads();  // the next chunk rewrites the prefix
   }
-  read = cc_block_sum<CC_BLOCK>(read, s_sum);
+  read = block_sum<CC_BLOCK>(read, s_sum);
   if (tid == 0 && read)
     atomicAdd(&ctr->edges, read);
 }
 
 /// The segments on the big list, one workgroup each: the part of a segment between 16-byte
 /// boundaries four entries per thread, its ends one entry per thread.
-inline __global__ void __launch_bounds__(CC_BLOCK)
+__global__ void __launch_bounds__(CC_BLOCK)
     cc_big_kernel(const int32_t* ap, const int32_t* aj, int32_t* parent, int32_t first, const int2* big,
                   const cc_counters_t* ctr) {
   const int32_t items = ctr->big_n;  // written by the remainder kernel before this one; constant here
@@ -261,14 +214,13 @@ inline __global__ void __launch_bounds__(CC_BLOCK)
 }
 
 /// Copy the counters to the host's mirror and stamp the hand-off: the last kernel of a call.
-inline __global__ void cc_publish_kernel(const cc_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
+__global__ void cc_publish_kernel(const cc_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
                                   unsigned long long sequence) {
   if (threadIdx.x == 0) {
     mirror[CC_EDGES] = ctr->edges;
     mirror[CC_COMPONENTS] = ctr->components;
     mirror[CC_GIANT] = (unsigned long long)(long long)ctr->giant;
-    __threadfence_system();
-    __hip_atomic_store(&mirror[sequence_slot], sequence, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    stamp_handoff(mirror, sequence_slot, sequence);
   }
 }
 

@@ -32,7 +32,7 @@
  */
 #pragma once
 
-#include <gunrock/hip/primitives.hxx>
+#include <gunrock/hip/kernels/row_walk.hxx>
 
 namespace gunrock {
 namespace hip {
@@ -57,16 +57,6 @@ struct kcore_counters_t {
 /// What the host reads per hand-off (words of the pinned mirror).
 enum { KC_HEAD = 0, KC_TAIL, KC_DEGSUM, KC_NEXT_K, KC_EDGES, KC_NONEMPTY, KC_MAX_ROW, KC_WORDS };
 
-template <typename T>
-__device__ __forceinline__ T kcore_wave_min(T x) {
-#pragma unroll
-  for (int d = wave_size / 2; d > 0; d >>= 1) {
-    T y = __shfl_xor(x, d, wave_size);
-    x = y < x ? y : x;
-  }
-  return x;
-}
-
 __global__ void __launch_bounds__(KCORE_BLOCK)
     kcore_init_kernel(const int32_t* ap, int32_t n, int32_t* deg, int32_t* core, kcore_counters_t* ctr) {
   unsigned mn = KCORE_NONE, mx = 0;
@@ -81,7 +71,7 @@ __global__ void __launch_bounds__(KCORE_BLOCK)
       mx = max(mx, (unsigned)d);
     }
   }
-  mn = kcore_wave_min(mn);
+  mn = wave_min(mn);
   mx = wave_max(mx);
   rows = wave_sum(rows);
   if (lane_id() == 0 && rows) {
@@ -111,8 +101,7 @@ __device__ __forceinline__ void kcore_publish(kcore_counters_t* ctr, unsigned lo
   ctr->degsum = 0;
   ctr->big_n = 0;
   ctr->next_k = level_over ? KCORE_NONE : next_k;
-  __threadfence_system();
-  __hip_atomic_store(&mirror[sequence_slot], sequence, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  stamp_handoff(mirror, sequence_slot, sequence);
 }
 
 /// The first hand-off: the first k, the longest row and the rows with entries.
@@ -151,7 +140,7 @@ __global__ void __launch_bounds__(KCORE_BLOCK)
       }
     }
   }
-  mn = kcore_wave_min(mn);
+  mn = wave_min(mn);
   dsum = wave_sum(dsum);
   if (lane == 0) {
     if (mn != KCORE_NONE)
@@ -159,19 +148,6 @@ __global__ void __launch_bounds__(KCORE_BLOCK)
     if (dsum)
       atomicAdd(&ctr->degsum, dsum);
   }
-}
-
-/// Smallest i in [0, cnt) with pre[i] > t (pre inclusive and non-decreasing, t < pre[cnt - 1]).
-__device__ __forceinline__ int kcore_owner(const int32_t* pre, int cnt, int32_t t) {
-  int lo = 0, hi = cnt - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (pre[mid] > t)
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  return lo;
 }
 
 /// Where a peel kernel appends the vertices whose degree crossed k.
@@ -202,7 +178,7 @@ __device__ __forceinline__ void kcore_relax(bool active, int32_t w, int32_t k, c
     if (cross) {
       const int32_t at = base + rank_in_mask(m);
       if (NARROW)  // read back by this workgroup in the next generation: past the L1
-        __hip_atomic_store(sink.queue + at, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        store_relaxed(sink.queue + at, w);
       else
         sink.queue[at] = w;
       dsum += (unsigned long long)(ap[w + 1] - ap[w]);
@@ -221,8 +197,7 @@ __device__ __forceinline__ int32_t kcore_peel_chunk(const int32_t* ap, const int
   const int tid = threadIdx.x;
   int32_t lo = 0, d = 0;
   if (a + tid < b) {
-    const int32_t u = NARROW ? __hip_atomic_load(sink.queue + a + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : sink.queue[a + tid];
+    const int32_t u = NARROW ? load_relaxed(sink.queue + a + tid) : sink.queue[a + tid];
     lo = ap[u];
     d = ap[u + 1] - lo;
     core[u] = k;
@@ -241,7 +216,7 @@ __device__ __forceinline__ int32_t kcore_peel_chunk(const int32_t* ap, const int
     const int32_t t = t0 + tid;
     int32_t w = 0;
     if (t < P)
-      w = aj[s_base[kcore_owner(s_pre, cnt, t)] + t];
+      w = aj[s_base[prefix_owner(s_pre, cnt, t)] + t];
     kcore_relax<NARROW>(t < P, w, k, ap, deg, sink, mn, dsum);
   }
   __syncthreads();  // the next chunk rewrites the prefix
@@ -251,7 +226,7 @@ __device__ __forceinline__ int32_t kcore_peel_chunk(const int32_t* ap, const int
 /// Flush a thread's running minimum and degree sum: one atomic pair per wavefront.
 __device__ __forceinline__ void kcore_flush(unsigned mn, unsigned long long dsum, unsigned* next_k,
                                             unsigned long long* degsum) {
-  mn = kcore_wave_min(mn);
+  mn = wave_min(mn);
   dsum = wave_sum(dsum);
   if (lane_id() == 0) {
     if (mn != KCORE_NONE)
@@ -335,7 +310,7 @@ __global__ void __launch_bounds__(KCORE_NARROW_BLOCK)
     if (threadIdx.x == 0)
       s_dsum = 0;  // appends come after the barriers of the next chunk's prefix sum
   }
-  mn = kcore_wave_min(mn);
+  mn = wave_min(mn);
   if (lane_id() == 0 && mn != KCORE_NONE)
     atomicMin(&s_min, mn);
   __syncthreads();

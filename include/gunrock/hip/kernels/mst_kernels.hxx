@@ -10,7 +10,7 @@
  *
  *   mst_init_kernel     comp[v] = v, best[v] = MST_NONE, done[v] = 0.
  *   mst_search_kernel   a chunk of MST_BLOCK consecutive rows per workgroup, their entries flattened
- *                       over the workgroup's threads as in cc_remainder_kernel.  An entry whose ends
+ *                       over the workgroup's threads (flat_walk, row_walk.hxx).  An entry whose ends
  *                       lie in different components offers its key to BOTH (pre-tested 64-bit atomic
  *                       min): the order includes the position, so the entry (v, u) stored in row v
  *                       is another candidate than (u, v).  A row none of whose entries left its
@@ -34,11 +34,11 @@
  * comp[] and best[] do not change while a kernel that reads them plainly runs (search reads comp and
  * changes best by atomics only; hook reads both and writes link and the bitmap; flatten reads link
  * and writes each thread's own comp word).  link[] IS read while other CUs write it (mst_jump_kernel):
- * those are relaxed agent-scope atomic loads and stores, as in cc_kernels.hxx.
+ * those are relaxed agent-scope atomic loads and stores (load_relaxed / store_relaxed).
  */
 #pragma once
 
-#include <gunrock/hip/kernels/cc_kernels.hxx>
+#include <gunrock/hip/kernels/row_walk.hxx>
 
 namespace gunrock {
 namespace hip {
@@ -80,7 +80,7 @@ __device__ __forceinline__ unsigned long long mst_key(float w, int32_t e) {
 
 /// Pre-tested atomic min: most offers lose, and a loser costs one L2-served load (util/math.hxx).
 __device__ __forceinline__ void mst_min(unsigned long long* p, unsigned long long key) {
-  if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key)
+  if (load_relaxed(p) > key)
     atomicMin(p, key);
 }
 
@@ -97,7 +97,7 @@ __device__ __forceinline__ int32_t mst_row_of(const int32_t* ap, int32_t n, int3
   return lo;
 }
 
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_init_kernel(int32_t* comp, unsigned long long* best, unsigned char* done, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)MST_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * MST_BLOCK) {
     comp[v] = (int32_t)v;
@@ -109,7 +109,7 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
 /// done[v]: 0 = walk the row, 1 = every entry is internal, 2 = a big row nobody has found an
 /// outgoing entry in (the big kernel writes 0 back when it finds one).  `use_flags` == 0: done[] is
 /// neither read nor written and every row is walked in every round.
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_search_kernel(const int32_t* ap, const int32_t* aj, const float* ax, const int32_t* comp,
                       unsigned long long* best, unsigned char* done, int32_t n, int use_flags, int32_t big_row,
                       int2* big, mst_counters_t* ctr) {
@@ -127,10 +127,7 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
       d = max(ap[v + 1] - lo, 0);
       c = comp[v];
       if (d > big_row) {
-        const int32_t segments = (d + MST_BIG_SEGMENT - 1) / MST_BIG_SEGMENT;
-        const int32_t at = atomicAdd(&ctr->big_n, segments);
-        for (int32_t k = 0; k < segments; ++k)
-          big[at + k] = make_int2((int32_t)v, k);
+        push_big_segments<MST_BIG_SEGMENT>(&ctr->big_n, big, (int32_t)v, d);
         if (use_flags)
           done[v] = 2;
         read += (unsigned long long)d;
@@ -140,38 +137,29 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
       }
     }
     s_live[tid] = 0;
-    int32_t P = 0;
-    const int32_t excl = block_exclusive_sum<MST_BLOCK>(d, P, s_wave);
-    if (P != 0) {  // uniform
-      s_pre[tid] = excl + d;
-      s_base[tid] = lo - excl;
-      s_comp[tid] = c;
-      __syncthreads();
-      for (int32_t t = tid; t < P; t += MST_BLOCK) {
-        const int o = cc_owner(s_pre, MST_BLOCK, t);
-        const int32_t e = s_base[o] + t;
-        const int32_t cu = s_comp[o], cv = comp[aj[e]];
-        if (cu != cv) {
-          const unsigned long long key = mst_key(ax[e], e);
-          mst_min(best + cu, key);
-          mst_min(best + cv, key);
-          s_live[o] = 1;
-        }
+    s_comp[tid] = c;
+    const int32_t P = flat_walk<MST_BLOCK>(d, lo, s_pre, s_base, s_wave, [&](int o, int32_t e) {
+      const int32_t cu = s_comp[o], cv = comp[aj[e]];
+      if (cu != cv) {
+        const unsigned long long key = mst_key(ax[e], e);
+        mst_min(best + cu, key);
+        mst_min(best + cv, key);
+        s_live[o] = 1;
       }
-      read += (unsigned long long)(tid == 0 ? P : 0);
-      __syncthreads();  // s_live is complete; the next chunk rewrites the prefix
-    }
+    });
+    read += (unsigned long long)(tid == 0 ? P : 0);
+    // s_live is complete behind flat_walk's trailing barrier (P == 0: nobody wrote it)
     if (use_flags && walked && !s_live[tid])
       done[v] = 1;
   }
-  read = cc_block_sum<MST_BLOCK>(read, s_sum);
+  read = block_sum<MST_BLOCK>(read, s_sum);
   if (tid == 0 && read)
     atomicAdd(&ctr->edges, read);
 }
 
 /// The segments on the big list, one workgroup each, consecutive threads on consecutive entries.
 /// The row's own component is the same for the whole segment: its keys are reduced per wave first.
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_big_kernel(const int32_t* ap, const int32_t* aj, const float* ax, const int32_t* comp,
                    unsigned long long* best, unsigned char* done, int use_flags, const int2* big,
                    const mst_counters_t* ctr) {
@@ -190,11 +178,7 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
         mine = key < mine ? key : mine;
       }
     }
-#pragma unroll
-    for (int s = wave_size / 2; s > 0; s >>= 1) {
-      const unsigned long long other = __shfl_xor(mine, s, wave_size);
-      mine = other < mine ? other : mine;
-    }
+    mine = wave_min(mine);
     if (lane_id() == 0 && mine != MST_NONE) {
       mst_min(best + cu, mine);
       if (use_flags)
@@ -203,7 +187,7 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
   }
 }
 
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_hook_kernel(const int32_t* ap, const int32_t* aj, const int32_t* comp, const unsigned long long* best,
                     int32_t* link, unsigned int* chosen, int32_t n, mst_counters_t* ctr) {
   __shared__ unsigned long long s_sum[MST_BLOCK / wave_size];
@@ -227,14 +211,14 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
     }
     link[r] = to;
   }
-  hooked = cc_block_sum<MST_BLOCK>(hooked, s_sum);
+  hooked = block_sum<MST_BLOCK>(hooked, s_sum);
   if (threadIdx.x == 0 && hooked)
     atomicAdd(&ctr->hooked, hooked);
 }
 
 /// Pass `pass` of the round's pointer jumping over the roots the hook kernel wrote.  A word always
 /// names an ancestor, a pass at least halves every root's distance to the top, in place or not.
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_jump_kernel(const int32_t* comp, int32_t* link, int32_t n, int pass, mst_counters_t* ctr) {
   if (pass > 0 && ctr->changed[pass - 1] == 0)  // written by the kernel before this one
     return;
@@ -242,21 +226,21 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
   for (int64_t v = blockIdx.x * (int64_t)MST_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * MST_BLOCK) {
     if (comp[v] != (int32_t)v)
       continue;
-    int32_t l = cc_load(link + v), ll = cc_load(link + l);
+    int32_t l = load_relaxed(link + v), ll = load_relaxed(link + l);
     if (l == ll)
       continue;
     for (int k = 0; k < 4 && l != ll; ++k) {
       l = ll;
-      ll = cc_load(link + l);
+      ll = load_relaxed(link + l);
     }
-    __hip_atomic_store(link + v, l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    store_relaxed(link + v, l);
     changed = true;
   }
   if (changed)
     ctr->changed[pass] = 1;  // every writer writes the same value
 }
 
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_flatten_kernel(int32_t* comp, const int32_t* link, unsigned long long* best, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)MST_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * MST_BLOCK) {
     comp[v] = link[comp[v]];  // comp[v] was a root of this round: the hook kernel wrote its word
@@ -265,7 +249,7 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
 }
 
 /// Copy the counters to the host's mirror, clear the round's, stamp the hand-off.
-inline __global__ void mst_publish_kernel(mst_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
+__global__ void mst_publish_kernel(mst_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
                                    unsigned long long sequence) {
   if (threadIdx.x == 0) {
     mirror[MST_EDGES] = ctr->edges;
@@ -276,27 +260,26 @@ inline __global__ void mst_publish_kernel(mst_counters_t* ctr, unsigned long lon
     ctr->big_n = 0;
     for (int j = 0; j < MST_MAX_JUMPS; ++j)
       ctr->changed[j] = 0;
-    __threadfence_system();
-    __hip_atomic_store(&mirror[sequence_slot], sequence, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    stamp_handoff(mirror, sequence_slot, sequence);
   }
 }
 
 // ---- labels: the smallest vertex id of each component (what grx_cc returns) ----------------------
 
-inline __global__ void __launch_bounds__(MST_BLOCK) mst_minid_init_kernel(int32_t* smallest, int32_t n) {
+__global__ void __launch_bounds__(MST_BLOCK) mst_minid_init_kernel(int32_t* smallest, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)MST_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * MST_BLOCK)
     smallest[v] = (int32_t)v;
 }
 
-inline __global__ void __launch_bounds__(MST_BLOCK) mst_minid_kernel(const int32_t* comp, int32_t* smallest, int32_t n) {
+__global__ void __launch_bounds__(MST_BLOCK) mst_minid_kernel(const int32_t* comp, int32_t* smallest, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)MST_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * MST_BLOCK) {
     const int32_t c = comp[v];
-    if ((int32_t)v < c && cc_load(smallest + c) > (int32_t)v)
+    if ((int32_t)v < c && load_relaxed(smallest + c) > (int32_t)v)
       atomicMin(smallest + c, (int32_t)v);
   }
 }
 
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_label_kernel(const int32_t* comp, const int32_t* smallest, int32_t* label, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)MST_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * MST_BLOCK)
     label[v] = smallest[comp[v]];
@@ -306,12 +289,12 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
 // A tile is MST_BLOCK words of the bitmap (a word per thread); whichever workgroup takes a tile
 // computes the same numbers, so nothing below depends on the schedule.
 
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_tile_count_kernel(const unsigned int* chosen, int64_t words, int64_t tiles, unsigned int* tile_count) {
   __shared__ unsigned long long s_sum[MST_BLOCK / wave_size];
   for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
     const int64_t w = t * MST_BLOCK + threadIdx.x;
-    const unsigned long long c = cc_block_sum<MST_BLOCK>(w < words ? (unsigned long long)__popc(chosen[w]) : 0ull, s_sum);
+    const unsigned long long c = block_sum<MST_BLOCK>(w < words ? (unsigned long long)__popc(chosen[w]) : 0ull, s_sum);
     if (threadIdx.x == 0)
       tile_count[t] = (unsigned int)c;
     __syncthreads();  // the next tile rewrites s_sum
@@ -319,7 +302,7 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
 }
 
 /// ONE workgroup: tile_count[] becomes its exclusive prefix, the total goes to the counters.
-inline __global__ void __launch_bounds__(MST_SCAN_BLOCK)
+__global__ void __launch_bounds__(MST_SCAN_BLOCK)
     mst_tile_scan_kernel(unsigned int* tile_count, int64_t tiles, mst_counters_t* ctr) {
   __shared__ unsigned long long s_wave[MST_SCAN_BLOCK / wave_size + 1];
   unsigned long long carry = 0;
@@ -352,7 +335,7 @@ __device__ __forceinline__ double mst_tree_sum(double x, double* s) {
 /// entries (may be NULL): position `tile_offset[tile] + rank` gets the rank-th chosen entry of the
 /// tile, so the whole array ascends.  tile_sum[tile]: the float64 sum of the tile's chosen weights,
 /// each thread's in ascending position, the threads' in a fixed tree.
-inline __global__ void __launch_bounds__(MST_BLOCK)
+__global__ void __launch_bounds__(MST_BLOCK)
     mst_emit_kernel(const unsigned int* chosen, const float* ax, int64_t words, int64_t tiles,
                     const unsigned int* tile_offset, int32_t* entries, int64_t capacity, double* tile_sum) {
   __shared__ unsigned int s_wave[MST_BLOCK / wave_size + 1];
@@ -380,7 +363,7 @@ inline __global__ void __launch_bounds__(MST_BLOCK)
 }
 
 /// ONE workgroup: thread i adds tiles i, i + BLOCK, ... in that order, then the fixed tree.
-inline __global__ void __launch_bounds__(MST_SCAN_BLOCK)
+__global__ void __launch_bounds__(MST_SCAN_BLOCK)
     mst_sum_kernel(const double* tile_sum, int64_t tiles, mst_counters_t* ctr) {
   __shared__ double s_tree[MST_SCAN_BLOCK];
   double sum = 0.0;

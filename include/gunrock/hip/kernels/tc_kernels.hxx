@@ -128,19 +128,6 @@ __global__ void tc_class_starts_kernel(const unsigned* keys, int32_t n, int32_t*
   starts[c] = lo;
 }
 
-/// Smallest i in [0, d) with pre[i] > t (pre inclusive, t < pre[d - 1]).
-__device__ __forceinline__ int32_t tc_owner(const int32_t* pre, int32_t d, int32_t t) {
-  int32_t lo = 0, hi = d - 1;
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (pre[mid] > t)
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  return lo;
-}
-
 /// Position of w in the sorted id[0, d), or -1.
 __device__ __forceinline__ int32_t tc_find(const int32_t* id, int32_t d, int32_t w) {
   int32_t lo = 0, hi = d;
@@ -213,7 +200,7 @@ __global__ void __launch_bounds__(TC_BLOCK)
     __syncthreads();
     unsigned mine = 0;
     for (int32_t t = l; t < P; t += G) {
-      const int32_t i = tc_owner(pre, d, t);
+      const int32_t i = prefix_owner(pre, d, t);
       const int32_t j = tc_find(id, d, laj[base[i] + t]);
       if (j >= 0) {
         ++mine;
@@ -294,7 +281,7 @@ __global__ void __launch_bounds__(TC_BLOCK)
     __syncthreads();
     unsigned mine = 0;
     for (int32_t t = tid; t < P; t += TC_BLOCK) {
-      const int32_t i = tc_owner(pre, d, t);
+      const int32_t i = prefix_owner(pre, d, t);
       const int32_t j = tc_find(id, d, laj[base[i] + t]);
       if (j >= 0) {
         ++mine;

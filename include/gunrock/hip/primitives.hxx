@@ -67,9 +67,44 @@ __device__ __forceinline__ T wave_max(T x) {
   return x;
 }
 
+template <typename T>
+__device__ __forceinline__ T wave_min(T x) {
+#pragma unroll
+  for (int d = wave_size / 2; d > 0; d >>= 1) {
+    T y = __shfl_xor(x, d, wave_size);
+    x = y < x ? y : x;
+  }
+  return x;
+}
+
+/// Relaxed agent-scope accesses to a word other CUs change while the kernel runs: a plain load may
+/// be answered by the CU's L1 for ever, or be hoisted out of a loop.
+template <typename T>
+__device__ __forceinline__ T load_relaxed(const T* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename T>
+__device__ __forceinline__ void store_relaxed(T* p, T x) {
+  __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---------------------------------------------------------------------------
 // workgroup level (BLOCK threads = BLOCK/64 wavefronts)
 // ---------------------------------------------------------------------------
+
+/// Sum over the workgroup, valid in thread 0.  `s_wave`: BLOCK / 64 words of LDS.  One barrier.
+template <int BLOCK, typename T>
+__device__ __forceinline__ T block_sum(T x, T* s_wave) {
+  x = wave_sum(x);
+  if (lane_id() == 0)
+    s_wave[threadIdx.x / wave_size] = x;
+  __syncthreads();
+  T total = 0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < BLOCK / wave_size; ++w)
+      total += s_wave[w];
+  return total;
+}
 
 /**
  * @brief Exclusive prefix sum over one value per thread.  `wave_totals` is LDS
@@ -109,6 +144,20 @@ __device__ __forceinline__ int rightmost_le(const K* keys, key_t key, int n) {
       lo = mid;
     else
       hi = mid;
+  }
+  return lo;
+}
+
+/// Smallest i in [0, cnt) with pre[i] > t (pre inclusive and non-decreasing, t < pre[cnt - 1]): the
+/// owner of flattened position t when pre[] is the inclusive prefix of the owners' lengths.
+__device__ __forceinline__ int prefix_owner(const int32_t* pre, int cnt, int32_t t) {
+  int lo = 0, hi = cnt - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (pre[mid] > t)
+      hi = mid;
+    else
+      lo = mid + 1;
   }
   return lo;
 }

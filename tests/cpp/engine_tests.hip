@@ -9,6 +9,7 @@
 #include <gunrock/algorithms/algorithms.hxx>
 #include <gunrock/graph/reorder.hxx>
 #include <gunrock/hip/algorithms.hxx>
+#include <gunrock/hip/kernels/row_walk.hxx>
 
 #include <algorithm>
 #include <cstdio>
@@ -77,6 +78,26 @@ struct toy_enactor_t : gunrock::enactor_t<problem_type> {
   using gunrock::enactor_t<problem_type>::enactor_t;
   void loop(gcuda::multi_context_t&) override {}
 };
+
+// one small kernel per workgroup helper of hip/primitives.hxx and hip/kernels/row_walk.hxx
+template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) block_sum_probe(const unsigned long long* in, unsigned long long* out) {
+  __shared__ unsigned long long s_wave[BLOCK / hip::wave_size];
+  const unsigned long long total = hip::block_sum<BLOCK>(in[threadIdx.x], s_wave);
+  if (threadIdx.x == 0)
+    *out = total;
+}
+__global__ void __launch_bounds__(64) wave_min_probe(const unsigned* in, unsigned* out) {
+  out[threadIdx.x] = hip::wave_min(in[threadIdx.x]);
+}
+__global__ void __launch_bounds__(64) prefix_owner_probe(const int* pre, int cnt, int n_t, int* out) {
+  if ((int)threadIdx.x < n_t)
+    out[threadIdx.x] = hip::prefix_owner(pre, cnt, (int)threadIdx.x);
+}
+__global__ void __launch_bounds__(64) push_big_probe(int* big_n, int2* big, int v, int d) {
+  if (threadIdx.x == 0)
+    hip::kernels::push_big_segments<4096>(big_n, big, v, d);
+}
 
 static FILE* dump = nullptr;
 template <typename T>
@@ -840,6 +861,69 @@ int main(int argc, char** argv) {
     dump_array("transpose_result_offsets", T.offsets.to_host());
     dump_array("transpose_result_indices", T.indices.to_host());
     dump_array("transpose_result_edge_ids", T.edge_ids.to_host());
+  }
+
+  // ---- workgroup helpers shared by the cc / mst / kcore / tc kernels, each against a host loop -----
+  {
+    auto block_sum_of = [&](auto block_tag, const std::vector<unsigned long long>& in) {
+      constexpr int BLOCK = decltype(block_tag)::value;
+      auto d_in = upload(in);
+      hip::device_array_t<unsigned long long> d_out(1);
+      block_sum_probe<BLOCK><<<1, BLOCK, 0, ctx.stream()>>>(d_in.data(), d_out.data());
+      ctx.synchronize();
+      return d_out.to_host()[0];
+    };
+    auto check_block_sum = [&](auto block_tag) {
+      constexpr int BLOCK = decltype(block_tag)::value;
+      std::vector<unsigned long long> zeros(BLOCK, 0), last(BLOCK, 0), wide(BLOCK);
+      last[BLOCK - 1] = 7;
+      for (int i = 0; i < BLOCK; ++i) wide[i] = (1ull << 32) + (unsigned long long)i + 1;  // the 64-bit sum carries
+      for (const auto& in : {zeros, last, wide})
+        CHECK(block_sum_of(block_tag, in) == std::accumulate(in.begin(), in.end(), 0ull));
+    };
+    check_block_sum(std::integral_constant<int, 256>());
+    check_block_sum(std::integral_constant<int, 1024>());
+
+    for (int at : {0, 63}) {  // the minimum at either end of the wavefront
+      std::vector<unsigned> in(64);
+      for (int i = 0; i < 64; ++i) in[i] = 1000u + (unsigned)((i * 37) % 64);
+      in[at] = 3;
+      auto d_in = upload(in);
+      hip::device_array_t<unsigned> d_out(64);
+      wave_min_probe<<<1, 64, 0, ctx.stream()>>>(d_in.data(), d_out.data());
+      ctx.synchronize();
+      CHECK(d_out.to_host() == std::vector<unsigned>(64, *std::min_element(in.begin(), in.end())));
+    }
+
+    auto check_prefix_owner = [&](const std::vector<int>& lengths) {
+      std::vector<int> pre(lengths.size());
+      std::partial_sum(lengths.begin(), lengths.end(), pre.begin());
+      const int cnt = (int)pre.size(), total = pre.back();
+      auto d_pre = upload(pre);
+      hip::device_array_t<int> d_out(total);
+      prefix_owner_probe<<<1, 64, 0, ctx.stream()>>>(d_pre.data(), cnt, total, d_out.data());
+      ctx.synchronize();
+      std::vector<int> want(total);
+      for (int t = 0; t < total; ++t)
+        want[t] = (int)(std::upper_bound(pre.begin(), pre.end(), t) - pre.begin());  // smallest i: pre[i] > t
+      CHECK(d_out.to_host() == want);
+    };
+    std::vector<int> lengths = {0, 0, 3, 0, 1, 0};  // leading, interior and trailing empty owners
+    lengths.resize(256, 0);
+    check_prefix_owner(lengths);
+    check_prefix_owner({5});  // a single owner
+
+    hip::device_array_t<int> big_n(1), big(2 * 8);
+    big_n.zero();
+    big.zero();
+    const int rows[3][2] = {{7, 4097}, {9, 8192}, {11, 4096}};  // 2, 2 and 1 segments of 4096
+    for (const auto& r : rows)
+      push_big_probe<<<1, 64, 0, ctx.stream()>>>(big_n.data(), reinterpret_cast<int2*>(big.data()), r[0], r[1]);
+    ctx.synchronize();
+    CHECK(big_n.to_host()[0] == 5);
+    auto pairs = big.to_host();
+    pairs.resize(2 * 5);
+    CHECK((pairs == std::vector<int>{7, 0, 7, 1, 9, 0, 9, 1, 11, 0}));
   }
 
   // ---- unsupported variants throw (reference advance.hxx:121-127) ---------------------------
