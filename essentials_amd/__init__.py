@@ -8,12 +8,13 @@ HIP library and fails loudly when it is missing.
 """
 from .api import (  # noqa: F401
     Context, Graph, Options, Stats, PartitionedPlan, LoadBalance, FilterAlgorithm, UniquifyAlgorithm, EdgeOp,
-    VertexOp, EngineError, bfs, sssp, pagerank, bc, tc, kcore, cc, mst, advance, filter, uniquify, library_path,
+    VertexOp, EngineError, bfs, sssp, pagerank, bc, tc, kcore, cc, mst, color, advance, filter, uniquify,
+    library_path,
     INT_UNREACHED, FLT_UNREACHED,
 )
 
 __all__ = [
     "Context", "Graph", "Options", "Stats", "PartitionedPlan", "LoadBalance", "FilterAlgorithm", "UniquifyAlgorithm",
-    "EdgeOp", "VertexOp", "EngineError", "bfs", "sssp", "pagerank", "bc", "tc", "kcore", "cc", "mst", "advance",
-    "filter", "uniquify", "library_path", "INT_UNREACHED", "FLT_UNREACHED",
+    "EdgeOp", "VertexOp", "EngineError", "bfs", "sssp", "pagerank", "bc", "tc", "kcore", "cc", "mst", "color",
+    "advance", "filter", "uniquify", "library_path", "INT_UNREACHED", "FLT_UNREACHED",
 ]

@@ -212,6 +212,7 @@ _SIGNATURES = {
     "grx_bc": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_tc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_kcore": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_color": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_cc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_mst": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP,
                           C.POINTER(_Options), C.POINTER(_Stats)]),
@@ -677,6 +678,35 @@ def kcore(ctx: Context, g: Graph, cores=None, options: Optional[Options] = None)
     _check(load_library().grx_kcore(ctx._h, g._h, _ptr(cores), C.byref(degeneracy), C.byref(o), C.byref(s)),
            "grx_kcore")
     return cores, int(degeneracy.value), Stats._from(s)
+
+
+def color(ctx: Context, g: Graph, colors=None, options: Optional[Options] = None):
+    """Greedy colouring of a symmetric CSR in largest-degree-first order -> (int32 colours on the
+    device, number of colours as an int, Stats).
+
+    colors[v] is the smallest colour >= 0 that no neighbour of larger key has, with key(v) =
+    (row length << 32) | fmix32(v) (include/essentials_amd.h): a function of the CSR alone, the
+    same on every call, and adjacent vertices never share a colour.  `colors`: int32 contiguous
+    tensor of V on the context's device, allocated when None and filled in place otherwise.
+    Stats.iterations is the depth of the priority DAG and Stats.edges_expanded equals 2 * nnz."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if colors is None:
+        colors = torch.empty(g.n_rows, dtype=torch.int32, device=device)
+    else:
+        if not isinstance(colors, torch.Tensor) or colors.dtype != torch.int32:
+            raise TypeError("color: colors must be an int32 torch tensor")
+        if colors.dim() != 1 or colors.numel() != g.n_rows or not colors.is_contiguous():
+            raise ValueError(f"color: colors must be a contiguous tensor of {g.n_rows} elements")
+        if colors.device != device:
+            raise ValueError(f"color: colors must live on {device}")
+    count = C.c_int32()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_color(ctx._h, g._h, _ptr(colors), C.byref(count), C.byref(o), C.byref(s)),
+           "grx_color")
+    return colors, int(count.value), Stats._from(s)
 
 
 def cc(ctx: Context, g: Graph, components=None, options: Optional[Options] = None):

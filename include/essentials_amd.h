@@ -298,6 +298,47 @@ int grx_tc(grx_context_t ctx, grx_graph_t g, int64_t* d_vertex_triangles,
  * is released when it returns. */
 int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int32_t* h_degeneracy,
               const grx_options* opt, grx_stats* stats);
+/* Graph colouring (the reference's color.hxx hands out two fresh colours per filter pass by
+ * rand()-style priorities, so no two runs agree; this is not a port of it).
+ * GREEDY COLOURING IN LARGEST-DEGREE-FIRST ORDER: a function of the CSR arrays alone, and the same
+ * call returns bit-identical results.  deg(v) is the length of row v as given (a repeated entry
+ * counts each time, a self loop once) and
+ *     key(v) = ((uint64_t)deg(v) << 32) | fmix32(v)
+ * where fmix32 is the 32-bit finaliser on the unsigned vertex id (h ^= h >> 16; h *= 0x85ebca6b;
+ * h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16): a bijection, so keys are distinct, the order is
+ * strict and total and there is no tie to break.  u PRECEDES v when u != v, u appears in row v and
+ * key(u) > key(v).  color[v] is the smallest integer >= 0 that is not the colour of a vertex that
+ * precedes v: exactly what sequential greedy colouring gives when it takes the vertices in
+ * descending key.  Self loops never constrain, a repeated entry constrains once, a vertex with an
+ * empty row gets 0; hence color[v] <= (distinct predecessors of v) <= deg(v), and adjacent vertices
+ * never share a colour.
+ * d_colors: device int32[V] out, overwritten, the caller's numbering.  h_num_colors: HOST out,
+ * 1 + the largest colour, 0 when V == 0.  At least one of the two must be non-NULL
+ * (GRX_ERR_INVALID_ARGUMENT otherwise); with d_colors == NULL the call works on an array of its own.
+ * Undirected input only: n_rows != n_cols is GRX_ERR_INVALID_ARGUMENT; a handle with in-edges
+ * attached, or a CSR that is not its own transpose (verified once when unknown), is
+ * GRX_ERR_UNSUPPORTED (a coloured vertex tells the vertices it precedes through its own row, which
+ * needs every edge stored from both ends).  V == 0 is GRX_OK with nothing written.  opt may be NULL;
+ * only collect_kernel_time is read, and max_iterations != 0 is GRX_ERR_INVALID_ARGUMENT.
+ * Method: Jones-Plassmann, data-driven.  One pass counts, per vertex, the entries of its row that
+ * name a predecessor; the vertices without any form generation 1.  A generation's vertices take
+ * their colours (a 64-bit mask of the predecessors' colours; when it is full, and for rows above
+ * GRX_COLOR_BIG_ROW entries (default 4096), a bitmap of GRX_COLOR_MEX_WINDOW colours (default and
+ * at most 2048) that moves up until a window has a gap) and lower the count of every vertex they
+ * precede; the decrement that reaches 0 puts that vertex into the next generation.  Generations of
+ * at most 1024 vertices and GRX_COLOR_NARROW_EDGES entries (default 16384; 0 = never) run inside one
+ * workgroup without the host.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels, batch by
+ * batch, when collect_kernel_time is set), advance_launches (kernel launches), iterations (the
+ * DEPTH OF THE PRIORITY DAG: depth(v) = 1 + the largest depth of a predecessor, 1 without one;
+ * iterations = the largest depth, 0 for V == 0 -- defined by the answer, not by how generations were
+ * batched), vertices_reached (vertices with a non-empty row), edges_traversed = nnz, edges_expanded
+ * = 2 * nnz (each entry is classified once when predecessors are counted and once when its row's
+ * vertex is coloured; re-reads inside one colouring do not count).  The call builds and uses no
+ * hot-first copy, leaves no state on the handle but the symmetry verdict and releases its workspace
+ * when it returns. */
+int grx_color(grx_context_t ctx, grx_graph_t g, int32_t* d_colors, int32_t* h_num_colors,
+              const grx_options* opt, grx_stats* stats);
 /* Connected components (no reference counterpart: the reference has no such algorithm).
  * Every row entry (u, v) joins u and v, whatever its direction: on a symmetric CSR the result is
  * the connected components, on a directed one the WEAKLY connected components.  Self loops and
