@@ -660,6 +660,22 @@ def tc(ctx: Context, g: Graph, counts=None, per_vertex: bool = True, options: Op
     return counts, int(total.value), Stats._from(s)
 
 
+def _vertex_output(ctx: Context, g: Graph, t, call: str, what: str):
+    """The int32 output tensor `what` of `call`: allocated when None, else checked to be a contiguous
+    tensor of V on the context's device."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if t is None:
+        return torch.empty(g.n_rows, dtype=torch.int32, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise TypeError(f"{call}: {what} must be an int32 torch tensor")
+    if t.dim() != 1 or t.numel() != g.n_rows or not t.is_contiguous():
+        raise ValueError(f"{call}: {what} must be a contiguous tensor of {g.n_rows} elements")
+    if t.device != device:
+        raise ValueError(f"{call}: {what} must live on {device}")
+    return t
+
+
 def kcore(ctx: Context, g: Graph, cores=None, options: Optional[Options] = None):
     """gunrock::kcore::run on a symmetric CSR -> (int32 core numbers on the device, degeneracy as an
     int, Stats).
@@ -689,17 +705,7 @@ def color(ctx: Context, g: Graph, colors=None, options: Optional[Options] = None
     same on every call, and adjacent vertices never share a colour.  `colors`: int32 contiguous
     tensor of V on the context's device, allocated when None and filled in place otherwise.
     Stats.iterations is the depth of the priority DAG and Stats.edges_expanded equals 2 * nnz."""
-    torch = _torch()
-    device = torch.device(f"cuda:{ctx.device}")
-    if colors is None:
-        colors = torch.empty(g.n_rows, dtype=torch.int32, device=device)
-    else:
-        if not isinstance(colors, torch.Tensor) or colors.dtype != torch.int32:
-            raise TypeError("color: colors must be an int32 torch tensor")
-        if colors.dim() != 1 or colors.numel() != g.n_rows or not colors.is_contiguous():
-            raise ValueError(f"color: colors must be a contiguous tensor of {g.n_rows} elements")
-        if colors.device != device:
-            raise ValueError(f"color: colors must live on {device}")
+    colors = _vertex_output(ctx, g, colors, "color", "colors")
     count = C.c_int32()
     o = (options or Options())._c()
     s = _Stats()
@@ -718,17 +724,7 @@ def cc(ctx: Context, g: Graph, components=None, options: Optional[Options] = Non
     `components`: int32 contiguous tensor of V on the context's device, allocated when None.
     Stats.vertices_reached is V - components; Stats.edges_expanded counts the row entries read, nnz
     unless the graph is known to be symmetric, when the rows of the largest component stay unread."""
-    torch = _torch()
-    device = torch.device(f"cuda:{ctx.device}")
-    if components is None:
-        components = torch.empty(g.n_rows, dtype=torch.int32, device=device)
-    else:
-        if not isinstance(components, torch.Tensor) or components.dtype != torch.int32:
-            raise TypeError("cc: components must be an int32 torch tensor")
-        if components.dim() != 1 or components.numel() != g.n_rows or not components.is_contiguous():
-            raise ValueError(f"cc: components must be a contiguous tensor of {g.n_rows} elements")
-        if components.device != device:
-            raise ValueError(f"cc: components must live on {device}")
+    components = _vertex_output(ctx, g, components, "cc", "components")
     count = C.c_int64()
     o = (options or Options())._c()
     s = _Stats()
@@ -749,28 +745,11 @@ def mst(ctx: Context, g: Graph, entries=None, components=None, options: Optional
     in place otherwise.  `components`: None (no labels), True (allocate them) or such a tensor of
     V; the labels are those of `cc`.  Stats.iterations is the number of Boruvka rounds and
     Stats.edges_expanded the row entries the minimum search read, summed over rounds."""
-    torch = _torch()
-    device = torch.device(f"cuda:{ctx.device}")
-
-    def checked(t, what):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
-            raise TypeError(f"mst: {what} must be an int32 torch tensor")
-        if t.dim() != 1 or t.numel() != g.n_rows or not t.is_contiguous():
-            raise ValueError(f"mst: {what} must be a contiguous tensor of {g.n_rows} elements")
-        if t.device != device:
-            raise ValueError(f"mst: {what} must live on {device}")
-        return t
-
-    if entries is None:
-        entries = torch.empty(g.n_rows, dtype=torch.int32, device=device)
-    else:
-        checked(entries, "entries")
-    if components is True:
-        components = torch.empty(g.n_rows, dtype=torch.int32, device=device)
-    elif components is False:
+    entries = _vertex_output(ctx, g, entries, "mst", "entries")
+    if components is False:
         components = None
     elif components is not None:
-        checked(components, "components")
+        components = _vertex_output(ctx, g, None if components is True else components, "mst", "components")
     count, weight = C.c_int64(), C.c_double()
     o = (options or Options())._c()
     s = _Stats()

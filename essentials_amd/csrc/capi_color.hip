@@ -7,8 +7,6 @@
 
 #include <gunrock/hip/kernels/color_kernels.hxx>
 
-#include <cstring>
-
 using namespace essentials_amd;
 
 namespace k = gunrock::hip::kernels;
@@ -82,28 +80,21 @@ extern "C" int grx_color(grx_context_t ctx, grx_graph_t g, int32_t* d_colors, in
                                                                segments.data(), ctr);
       launches += 3;
       narrow();
-      const bool has_big = m[k::CL_MAX_ROW] > (unsigned long long)big_row;
-      // every batch consumes its generation: queue slots, of which there are n
-      while (m[k::CL_TAIL] > m[k::CL_HEAD]) {
-        const int32_t head = (int32_t)m[k::CL_HEAD], tail = (int32_t)m[k::CL_TAIL];
-        const int32_t count = tail - head;
-        const int32_t chunk = std::max(1, std::min<int32_t>(k::COLOR_BLOCK, (count + (int32_t)most - 1) / (int32_t)most));
-        clock.begin_batch();
-        k::color_wide_kernel<<<grid_for((std::size_t)count, (std::size_t)chunk, sc), k::COLOR_BLOCK, 0, s>>>(
-            g->d_ap, g->d_aj, pending.data(), color, queue.data(), n, head, tail, chunk, big_row, big.data(), window,
-            ctr);
-        ++launches;
-        if (has_big) {
-          k::color_big_kernel<<<(unsigned)sc.compute_units() * 4, k::COLOR_BLOCK, 0, s>>>(
-              g->d_ap, g->d_aj, pending.data(), color, queue.data(), n, big.data(), window, ctr);
-          ++launches;
-        }
-        ++generations;
-        narrow();
-      }
+      const bool has_big = m[k::GQ_MAX_ROW] > (unsigned long long)big_row;
+      generations = (unsigned long long)run_generations(
+          sc, clock, m, k::COLOR_BLOCK, has_big, launches,
+          [&](int32_t head, int32_t tail, int32_t chunk, unsigned grid) {
+            k::color_wide_kernel<<<grid, k::COLOR_BLOCK, 0, s>>>(g->d_ap, g->d_aj, pending.data(), color, queue.data(), n,
+                                                                head, tail, chunk, big_row, big.data(), window, ctr);
+          },
+          [&](unsigned grid) {
+            k::color_big_kernel<<<grid, k::COLOR_BLOCK, 0, s>>>(g->d_ap, g->d_aj, pending.data(), color, queue.data(), n,
+                                                               big.data(), window, ctr);
+          },
+          narrow);
       generations += m[k::CL_GENERATIONS];
-      edges = m[k::CL_EDGES];
-      nonempty = m[k::CL_NONEMPTY];
+      edges = m[k::GQ_EDGES];
+      nonempty = m[k::GQ_NONEMPTY];
       max_color = m[k::CL_MAX_COLOR];
       clock.stop_and_wait();
     }
@@ -111,15 +102,7 @@ extern "C" int grx_color(grx_context_t ctx, grx_graph_t g, int32_t* d_colors, in
 
     if (h_num_colors)
       *h_num_colors = (int32_t)max_color + 1;
-    if (stats) {
-      stats->elapsed_ms = clock.elapsed_ms();
-      stats->advance_kernel_ms = clock.kernel_ms();
-      stats->iterations = (int32_t)generations;
-      stats->advance_launches = launches;
-      stats->vertices_reached = (int64_t)nonempty;
-      stats->edges_traversed = (int64_t)g->nnz;
-      stats->edges_expanded = (int64_t)edges;
-    }
+    queue_call_stats(stats, clock, (int32_t)generations, launches, nonempty, (int64_t)g->nnz, edges);
     return (int)GRX_OK;
   });
 }

@@ -6,8 +6,6 @@
 
 #include <gunrock/hip/kernels/kcore_kernels.hxx>
 
-#include <cstring>
-
 using namespace essentials_amd;
 
 namespace k = gunrock::hip::kernels;
@@ -57,14 +55,13 @@ extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int3
       GRX_HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof *ctr, s));
       GRX_HIP_CHECK(hipMemsetAsync(&ctr->next_k, 0xff, sizeof ctr->next_k, s));  // KCORE_NONE
 
-      const unsigned most = (unsigned)sc.compute_units() * 8;
       const unsigned scan_grid = grid_for((std::size_t)n, k::KCORE_BLOCK, sc);
       // the hand-off that ends a batch is the narrow kernel's last act
       unsigned long long* m = nullptr;
       auto narrow = [&](int32_t level) {
         m = hand_off(sc, clock, [&](unsigned long long* mirror, int slot, unsigned long long seq) {
           k::kcore_narrow_kernel<<<1, k::KCORE_NARROW_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(), core, queue.data(),
-                                                                    level, k::KCORE_NARROW_BLOCK, narrow_edges, ctr,
+                                                                    n, level, k::KCORE_NARROW_BLOCK, narrow_edges, ctr,
                                                                     mirror, slot, seq);
         });
         ++launches;
@@ -76,58 +73,44 @@ extern "C" int grx_kcore(grx_context_t ctx, grx_graph_t g, int32_t* d_core, int3
         k::kcore_publish_kernel<<<1, 64, 0, s>>>(ctr, mirror, slot, seq);
       });
       launches += 2;
-      const bool has_big = m[k::KC_MAX_ROW] > (unsigned long long)big_row;
-      nonempty = m[k::KC_NONEMPTY];
+      const bool has_big = m[k::GQ_MAX_ROW] > (unsigned long long)big_row;
+      nonempty = m[k::GQ_NONEMPTY];
       int32_t k_prev = 0;
       // each level removes at least the vertex whose degree named it
       while ((unsigned)m[k::KC_NEXT_K] != k::KCORE_NONE) {
         const int32_t level = (int32_t)m[k::KC_NEXT_K];
-        const unsigned long long queued_before = m[k::KC_TAIL];
+        const unsigned long long queued_before = m[k::GQ_TAIL];
         clock.begin_batch();
         k::kcore_seed_kernel<<<scan_grid, k::KCORE_BLOCK, 0, s>>>(g->d_ap, deg.data(), n, k_prev, level, queue.data(), ctr);
         ++launches;
         narrow(level);
-        // every round consumes its generation: queue slots, of which there are n
-        while (m[k::KC_TAIL] > m[k::KC_HEAD]) {
-          const int32_t head = (int32_t)m[k::KC_HEAD], tail = (int32_t)m[k::KC_TAIL];
-          const int32_t count = tail - head;
-          const int32_t chunk = std::max(1, std::min<int32_t>(k::KCORE_BLOCK, (count + (int32_t)most - 1) / (int32_t)most));
-          const unsigned grid = grid_for((std::size_t)count, (std::size_t)chunk, sc);
-          clock.begin_batch();
-          k::kcore_wide_kernel<<<grid, k::KCORE_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(), core, queue.data(), head, tail,
-                                                              chunk, level, big_row, big.data(), ctr);
-          ++launches;
-          if (has_big) {
-            k::kcore_big_kernel<<<(unsigned)sc.compute_units() * 4, k::KCORE_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(),
-                                                                                          queue.data(), level, big.data(), ctr);
-            ++launches;
-          }
-          narrow(level);
-        }
+        run_generations(
+            sc, clock, m, k::KCORE_BLOCK, has_big, launches,
+            [&](int32_t head, int32_t tail, int32_t chunk, unsigned grid) {
+              k::kcore_wide_kernel<<<grid, k::KCORE_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(), core, queue.data(), n, head,
+                                                                  tail, chunk, level, big_row, big.data(), ctr);
+            },
+            [&](unsigned grid) {
+              k::kcore_big_kernel<<<grid, k::KCORE_BLOCK, 0, s>>>(g->d_ap, g->d_aj, deg.data(), queue.data(), n, level,
+                                                                 big.data(), ctr);
+            },
+            [&] { narrow(level); });
         k_prev = level;
         // the seed scan's smallest degree above k may belong to a vertex that left later in that
         // level: then nobody has this degree, the level is empty and names the next one exactly
-        if (m[k::KC_TAIL] > queued_before) {
+        if (m[k::GQ_TAIL] > queued_before) {
           ++levels;
           degeneracy = level;
         }
       }
-      edges = m[k::KC_EDGES];
+      edges = m[k::GQ_EDGES];
       clock.stop_and_wait();
     }
     hip::block_cache_t::instance().trim();
 
     if (h_degeneracy)
       *h_degeneracy = degeneracy;
-    if (stats) {
-      stats->elapsed_ms = clock.elapsed_ms();
-      stats->advance_kernel_ms = clock.kernel_ms();
-      stats->iterations = levels;
-      stats->advance_launches = launches;
-      stats->vertices_reached = (int64_t)nonempty;
-      stats->edges_traversed = (int64_t)edges;
-      stats->edges_expanded = (int64_t)edges;
-    }
+    queue_call_stats(stats, clock, levels, launches, nonempty, (int64_t)edges, edges);
     return (int)GRX_OK;
   });
 }

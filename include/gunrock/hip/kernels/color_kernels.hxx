@@ -41,7 +41,7 @@
  */
 #pragma once
 
-#include <gunrock/hip/kernels/row_walk.hxx>
+#include <gunrock/hip/kernels/generation_queue.hxx>
 
 namespace gunrock {
 namespace hip {
@@ -55,19 +55,13 @@ constexpr int COLOR_BIG_SEGMENT = 4096;    // the init pass cuts them into segme
 constexpr int COLOR_MEX_WINDOW = 2048;     // colours per LDS window: default and largest
 constexpr int COLOR_NO_COLOR = 0x7fffffff;
 
-/// Device counters of one grx_color call.
-struct color_counters_t {
-  int head, tail;             // the pending generation: queue[head, tail)
-  int big_n;                  // items on the big list (init: segments; a generation: rows)
-  int max_color;              // largest colour written
-  unsigned long long degsum;  // entries of the pending generation's rows
-  unsigned long long edges;   // entries classified so far
-  unsigned long long nonempty;  // rows with entries
+/// Device counters of one grx_color call (big_n: segments during init, rows in a generation).
+struct color_counters_t : queue_counters_t {
+  int max_color, pad;              // largest colour written
   unsigned long long generations;  // generations the narrow kernel ran
-  unsigned max_row, pad;
 };
-/// What the host reads per hand-off (words of the pinned mirror).
-enum { CL_HEAD = 0, CL_TAIL, CL_DEGSUM, CL_EDGES, CL_NONEMPTY, CL_MAX_ROW, CL_MAX_COLOR, CL_GENERATIONS, CL_WORDS };
+/// The mirror words the host reads per hand-off besides the queue's.
+enum { CL_MAX_COLOR = GQ_WORDS, CL_GENERATIONS, CL_WORDS };
 
 /// The 32-bit finaliser: a bijection on the unsigned vertex id.
 __host__ __device__ __forceinline__ unsigned color_fmix32(unsigned h) {
@@ -83,47 +77,15 @@ __device__ __forceinline__ unsigned long long color_key(const int32_t* ap, int32
   return ((unsigned long long)(unsigned)(ap[v + 1] - ap[v]) << 32) | color_fmix32((unsigned)v);
 }
 
-/// Where a kernel appends the vertices whose last predecessor it coloured.
-struct color_sink_t {
-  int32_t* queue;
-  int32_t n;                   // queue slots
-  int* tail;                   // global (init, wide, big) or LDS (narrow)
-  unsigned long long* degsum;  // likewise
-};
-
-/// Append w for the lanes with `ready`; every lane of the wavefront calls it.
-template <bool NARROW>
-__device__ __forceinline__ void color_append(bool ready, int32_t w, const int32_t* ap, const color_sink_t& sink,
-                                             unsigned long long& dsum) {
-  const unsigned long long m = __ballot(ready);
-  if (m) {
-    const int first = __ffsll((long long)m) - 1;
-    int32_t base = 0;
-    if (lane_id() == first)
-      base = atomicAdd(sink.tail, __popcll(m));
-    base = __shfl(base, first, wave_size);
-    if (ready) {
-      const int32_t at = base + rank_in_mask(m);
-      if (at < sink.n) {  // a vertex is queued once, so this holds; it guards the store all the same
-        if (NARROW)       // read back by this workgroup in the next generation: past the L1
-          store_relaxed(sink.queue + at, w);
-        else
-          sink.queue[at] = w;
-      }
-      dsum += (unsigned long long)(ap[w + 1] - ap[w]);
-    }
-  }
-}
-
 /// One entry naming a vertex w that the row's vertex precedes (`down` lanes hold one): one
 /// predecessor less; every lane of the wavefront calls it.
 template <bool NARROW>
 __device__ __forceinline__ void color_notify(bool down, int32_t w, const int32_t* ap, int32_t* pending,
-                                             const color_sink_t& sink, unsigned long long& dsum) {
+                                             const queue_sink_t& sink, unsigned long long& dsum) {
   bool ready = false;
   if (down)
     ready = atomicSub(&pending[w], 1) == 1;
-  color_append<NARROW>(ready, w, ap, sink, dsum);
+  queue_append<NARROW>(ready, w, ap, sink, dsum);
 }
 
 template <bool NARROW>
@@ -145,7 +107,7 @@ __device__ __forceinline__ void color_set(int32_t* color, int32_t v, int32_t c) 
 template <int BLOCK, bool NARROW>
 __device__ __forceinline__ int32_t color_block_mex(const int32_t* ap, const int32_t* aj, const int32_t* color,
                                                    int32_t* pending, int32_t v, int32_t base, int32_t window,
-                                                   bool relax, const color_sink_t& sink, unsigned* s_bits,
+                                                   bool relax, const queue_sink_t& sink, unsigned* s_bits,
                                                    int32_t* s_found, unsigned long long& dsum) {
   const int tid = threadIdx.x;
   const int32_t lo = ap[v], hi = ap[v + 1];
@@ -210,54 +172,39 @@ struct color_chunk_lds_t {
 template <int BLOCK, bool NARROW>
 __device__ __forceinline__ int32_t color_chunk(const int32_t* ap, const int32_t* aj, int32_t* pending, int32_t* color,
                                                int32_t a, int32_t b, int32_t big_row, int32_t* big, int32_t window,
-                                               color_counters_t* ctr, const color_sink_t& sink,
+                                               color_counters_t* ctr, const queue_sink_t& sink,
                                                color_chunk_lds_t<BLOCK>& s, int32_t& mx, unsigned long long& dsum) {
   const int tid = threadIdx.x;
-  int32_t v = -1, lo = 0, d = 0;
-  unsigned long long kv = 0;
-  if (a + tid < b) {
-    v = NARROW ? load_relaxed(sink.queue + a + tid) : sink.queue[a + tid];
-    lo = ap[v];
-    d = ap[v + 1] - lo;
-    kv = ((unsigned long long)(unsigned)d << 32) | color_fmix32((unsigned)v);
-    if (!NARROW && d > big_row) {
-      big[atomicAdd(&ctr->big_n, 1)] = v;
-      d = 0;
-      v = -1;
-    }
-  }
-  s.key[tid] = kv;
+  int32_t v = -1;
   s.mask[tid] = 0;
-  s.vert[tid] = v;
   if (tid == 0)
     s.n_over = 0;
-  int32_t P = 0;
-  const int32_t excl = block_exclusive_sum<BLOCK>(d, P, s.wave);
-  s.pre[tid] = excl + d;
-  s.base[tid] = lo - excl;
-  __syncthreads();
-  const int cnt = b - a;
-  for (int32_t t0 = 0; t0 < P; t0 += BLOCK) {
-    const int32_t t = t0 + tid;
-    bool down = false;
-    int32_t u = 0;
-    if (t < P) {
-      const int o = prefix_owner(s.pre, cnt, t);
-      u = aj[s.base[o] + t];
-      if (u != s.vert[o]) {
-        if (color_key(ap, u) > s.key[o]) {
-          const int32_t c = color_of<NARROW>(color, u);
-          // neighbouring lanes share an owner and often a colour: test before the atomic
-          if ((unsigned)c < 64u && !((__hip_atomic_load(&s.mask[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> c) & 1))
-            atomicOr(&s.mask[o], 1ull << c);
-        } else {
-          down = true;
+  const int32_t P = queue_walk<BLOCK, NARROW>(
+      ap, sink.queue, a, b, s.pre, s.base, s.wave,
+      [&](int32_t u, int32_t, int32_t& d) {
+        s.key[tid] = ((unsigned long long)(unsigned)d << 32) | color_fmix32((unsigned)u);
+        if (NARROW || !queue_divert_big(u, d, big_row, big, &ctr->big_n))
+          v = u;
+        s.vert[tid] = v;
+      },
+      [&](bool live, int o, int32_t e) {
+        bool down = false;
+        int32_t u = 0;
+        if (live) {
+          u = aj[e];
+          if (u != s.vert[o]) {
+            if (color_key(ap, u) > s.key[o]) {
+              const int32_t c = color_of<NARROW>(color, u);
+              // neighbouring lanes share an owner and often a colour: test before the atomic
+              if ((unsigned)c < 64u && !((__hip_atomic_load(&s.mask[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> c) & 1))
+                atomicOr(&s.mask[o], 1ull << c);
+            } else {
+              down = true;
+            }
+          }
         }
-      }
-    }
-    color_notify<NARROW>(down, u, ap, pending, sink, dsum);
-  }
-  __syncthreads();
+        color_notify<NARROW>(down, u, ap, pending, sink, dsum);
+      });
   if (v >= 0) {
     const unsigned long long absent = ~s.mask[tid];
     if (absent) {
@@ -283,17 +230,11 @@ __device__ __forceinline__ int32_t color_chunk(const int32_t* ap, const int32_t*
   return P;
 }
 
-/// Flush a thread's degree sum and largest colour: one atomic pair per wavefront.
-__device__ __forceinline__ void color_flush(int32_t mx, unsigned long long dsum, int* max_color,
-                                            unsigned long long* degsum) {
+/// Flush a thread's largest colour: one atomic per wavefront.
+__device__ __forceinline__ void color_flush_max(int32_t mx, int* max_color) {
   mx = wave_max(mx);
-  dsum = wave_sum(dsum);
-  if (lane_id() == 0) {
-    if (mx > 0)
-      atomicMax(max_color, mx);
-    if (dsum)
-      atomicAdd(degsum, dsum);
-  }
+  if (lane_id() == 0 && mx > 0)
+    atomicMax(max_color, mx);
 }
 
 __global__ void __launch_bounds__(COLOR_BLOCK)
@@ -303,7 +244,7 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
   __shared__ int32_t s_count[COLOR_BLOCK];
   __shared__ unsigned long long s_key[COLOR_BLOCK];
   const int tid = threadIdx.x;
-  const color_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
+  const queue_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
   unsigned long long dsum = 0, walked = 0, rows = 0;
   unsigned mxrow = 0;
   for (int64_t v0 = (int64_t)blockIdx.x * COLOR_BLOCK; v0 < n; v0 += (int64_t)gridDim.x * COLOR_BLOCK) {
@@ -340,15 +281,13 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
       color[v] = -1;
       ready = !is_big && count == 0;
     }
-    color_append<false>(ready, (int32_t)v, ap, sink, dsum);
+    queue_append<false>(ready, (int32_t)v, ap, sink, dsum);
   }
-  dsum = wave_sum(dsum);
+  queue_flush(dsum, &ctr->degsum);
   rows = wave_sum(rows);
   walked = wave_sum(walked);
   mxrow = wave_max(mxrow);
   if (lane_id() == 0) {
-    if (dsum)
-      atomicAdd(&ctr->degsum, dsum);
     if (rows)
       atomicAdd(&ctr->nonempty, rows);
     if (walked)
@@ -386,10 +325,10 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
 __global__ void __launch_bounds__(COLOR_NARROW_BLOCK)
     color_ready_kernel(const int32_t* ap, const int32_t* pending, int32_t* queue, int32_t n, const int2* big,
                        color_counters_t* ctr) {
-  const color_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
+  const queue_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
   const int32_t items = ctr->big_n;
   unsigned long long dsum = 0;
-  // whole wavefronts run every trip: the ballot of color_append sees all 64 lanes
+  // whole wavefronts run every trip: the ballot of queue_append sees all 64 lanes
   for (int32_t i0 = 0; i0 < items; i0 += COLOR_NARROW_BLOCK) {
     const int32_t i = i0 + threadIdx.x;
     bool ready = false;
@@ -399,11 +338,9 @@ __global__ void __launch_bounds__(COLOR_NARROW_BLOCK)
       v = item.x;
       ready = item.y == 0 && pending[v] == 0;
     }
-    color_append<false>(ready, v, ap, sink, dsum);
+    queue_append<false>(ready, v, ap, sink, dsum);
   }
-  dsum = wave_sum(dsum);
-  if (lane_id() == 0 && dsum)
-    atomicAdd(&ctr->degsum, dsum);
+  queue_flush(dsum, &ctr->degsum);
   __syncthreads();
   if (threadIdx.x == 0)
     ctr->big_n = 0;  // the generations' list starts empty
@@ -414,7 +351,7 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
                       int32_t head, int32_t tail, int32_t chunk, int32_t big_row, int32_t* big, int32_t window,
                       color_counters_t* ctr) {
   __shared__ color_chunk_lds_t<COLOR_BLOCK> s;
-  const color_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
+  const queue_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
   int32_t mx = 0;
   unsigned long long dsum = 0, walked = 0;
   for (int64_t a = head + (int64_t)blockIdx.x * chunk; a < tail; a += (int64_t)gridDim.x * chunk) {
@@ -422,7 +359,8 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
     walked += (unsigned long long)color_chunk<COLOR_BLOCK, false>(ap, aj, pending, color, (int32_t)a, b, big_row, big,
                                                                  window, ctr, sink, s, mx, dsum);
   }
-  color_flush(mx, dsum, &ctr->max_color, &ctr->degsum);
+  color_flush_max(mx, &ctr->max_color);
+  queue_flush(dsum, &ctr->degsum);
   if (threadIdx.x == 0 && walked)
     atomicAdd(&ctr->edges, walked);
 }
@@ -434,7 +372,7 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
                      const int32_t* big, int32_t window, color_counters_t* ctr) {
   __shared__ unsigned s_bits[COLOR_MEX_WINDOW / 32];
   __shared__ int32_t s_found;
-  const color_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
+  const queue_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
   const int32_t rows = ctr->big_n;  // written by the wide kernel before this one; constant here
   int32_t mx = 0;
   unsigned long long dsum = 0, walked = 0;
@@ -448,7 +386,8 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
       walked += (unsigned long long)(ap[v + 1] - ap[v]);
     }
   }
-  color_flush(mx, dsum, &ctr->max_color, &ctr->degsum);
+  color_flush_max(mx, &ctr->max_color);
+  queue_flush(dsum, &ctr->degsum);
   if (threadIdx.x == 0 && walked)
     atomicAdd(&ctr->edges, walked);
 }
@@ -462,57 +401,25 @@ __global__ void __launch_bounds__(COLOR_NARROW_BLOCK)
   __shared__ color_chunk_lds_t<COLOR_NARROW_BLOCK> s;
   __shared__ int s_tail, s_max;
   __shared__ unsigned long long s_dsum;
-  int32_t head = ctr->head, tail = min(ctr->tail, n);
-  unsigned long long degsum = ctr->degsum, walked = 0, generations = 0;
-  if (threadIdx.x == 0) {
-    s_tail = tail;
+  if (threadIdx.x == 0)
     s_max = ctr->max_color;
-    s_dsum = 0;
-  }
-  __syncthreads();
-  const color_sink_t sink{queue, n, &s_tail, &s_dsum};
   int32_t mx = 0;
-  // every trip consumes queue slots, and a vertex is queued once: at most V trips
-  while (tail > head && tail - head <= max_vertices && degsum <= max_edges) {
-    unsigned long long dsum = 0;
-    walked += (unsigned long long)color_chunk<COLOR_NARROW_BLOCK, true>(ap, aj, pending, color, head, tail, 0, nullptr,
-                                                                       window, ctr, sink, s, mx, dsum);
-    ++generations;
-    dsum = wave_sum(dsum);
-    if (lane_id() == 0 && dsum)
-      atomicAdd(&s_dsum, dsum);
-    __syncthreads();
-    head = tail;
-    tail = min(s_tail, n);
-    degsum = s_dsum;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      s_dsum = 0;  // appends come after the barriers of the next chunk's prefix sum
-  }
-  mx = wave_max(mx);
-  if (lane_id() == 0 && mx > 0)
-    atomicMax(&s_max, mx);
+  const narrow_result_t r = narrow_generations(
+      ctr, queue, n, max_vertices, max_edges, &s_tail, &s_dsum,
+      [&](int32_t head, int32_t tail, const queue_sink_t& sink, unsigned long long& dsum) {
+        return color_chunk<COLOR_NARROW_BLOCK, true>(ap, aj, pending, color, head, tail, 0, nullptr, window, ctr, sink,
+                                                     s, mx, dsum);
+      });
+  color_flush_max(mx, &s_max);
   __syncthreads();
   if (threadIdx.x == 0) {
     // no other kernel of the call runs beside this one
-    ctr->edges += walked;
-    ctr->generations += generations;
+    ctr->edges += r.walked;
+    ctr->generations += r.generations;
     ctr->max_color = s_max;
-    mirror[CL_HEAD] = (unsigned long long)head;
-    mirror[CL_TAIL] = (unsigned long long)tail;
-    mirror[CL_DEGSUM] = degsum;
-    mirror[CL_EDGES] = ctr->edges;
-    mirror[CL_NONEMPTY] = ctr->nonempty;
-    mirror[CL_MAX_ROW] = ctr->max_row;
     mirror[CL_MAX_COLOR] = (unsigned long long)s_max;
     mirror[CL_GENERATIONS] = ctr->generations;
-    // a pending generation goes to the wide kernel, which consumes all of it and gathers the
-    // entries of the one behind it
-    ctr->head = tail;
-    ctr->tail = tail;
-    ctr->degsum = 0;
-    ctr->big_n = 0;
-    stamp_handoff(mirror, sequence_slot, sequence);
+    queue_publish(ctr, mirror, sequence_slot, sequence, r.head, r.tail, r.degsum);
   }
 }
 

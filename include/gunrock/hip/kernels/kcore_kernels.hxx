@@ -32,7 +32,7 @@
  */
 #pragma once
 
-#include <gunrock/hip/kernels/row_walk.hxx>
+#include <gunrock/hip/kernels/generation_queue.hxx>
 
 namespace gunrock {
 namespace hip {
@@ -45,17 +45,11 @@ constexpr int KCORE_BIG_ROW = 4096;        // default: longer rows are walked by
 constexpr unsigned KCORE_NONE = 0xffffffffu;
 
 /// Device counters of one grx_kcore call.
-struct kcore_counters_t {
-  int head, tail;             // the pending generation: queue[head, tail)
-  unsigned next_k;            // smallest remaining degree above the level's k (KCORE_NONE: none)
-  int big_n;                  // rows on the big list
-  unsigned long long degsum;  // entries of the pending generation's rows
-  unsigned long long edges;   // row entries walked so far
-  unsigned long long nonempty;  // rows with entries
-  unsigned max_row, pad;
+struct kcore_counters_t : queue_counters_t {
+  unsigned next_k, pad;  // smallest remaining degree above the level's k (KCORE_NONE: none)
 };
-/// What the host reads per hand-off (words of the pinned mirror).
-enum { KC_HEAD = 0, KC_TAIL, KC_DEGSUM, KC_NEXT_K, KC_EDGES, KC_NONEMPTY, KC_MAX_ROW, KC_WORDS };
+/// The mirror word the host reads per hand-off besides the queue's.
+enum { KC_NEXT_K = GQ_WORDS, KC_WORDS };
 
 __global__ void __launch_bounds__(KCORE_BLOCK)
     kcore_init_kernel(const int32_t* ap, int32_t n, int32_t* deg, int32_t* core, kcore_counters_t* ctr) {
@@ -81,27 +75,14 @@ __global__ void __launch_bounds__(KCORE_BLOCK)
   }
 }
 
-/// Copy the counters to the host's mirror and stamp the hand-off.  One thread, last in its kernel.
-/// `level_over`: nothing is pending, so the next level's seed scan starts next_k afresh.
+/// The hand-off: ONE thread, last in its kernel.  When nothing is pending the level is over, and
+/// the next level's seed scan starts next_k afresh.
 __device__ __forceinline__ void kcore_publish(kcore_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
                                               unsigned long long sequence, int head, int tail,
                                               unsigned long long degsum, unsigned next_k) {
-  const bool level_over = head == tail;
-  mirror[KC_HEAD] = (unsigned long long)head;
-  mirror[KC_TAIL] = (unsigned long long)tail;
-  mirror[KC_DEGSUM] = degsum;
   mirror[KC_NEXT_K] = next_k;
-  mirror[KC_EDGES] = ctr->edges;
-  mirror[KC_NONEMPTY] = ctr->nonempty;
-  mirror[KC_MAX_ROW] = ctr->max_row;
-  // a pending generation goes to the wide kernel, which consumes all of it and gathers the
-  // entries of the one behind it
-  ctr->head = tail;
-  ctr->tail = tail;
-  ctr->degsum = 0;
-  ctr->big_n = 0;
-  ctr->next_k = level_over ? KCORE_NONE : next_k;
-  stamp_handoff(mirror, sequence_slot, sequence);
+  ctr->next_k = head == tail ? KCORE_NONE : next_k;
+  queue_publish(ctr, mirror, sequence_slot, sequence, head, tail, degsum);
 }
 
 /// The first hand-off: the first k, the longest row and the rows with entries.
@@ -111,14 +92,22 @@ __global__ void kcore_publish_kernel(kcore_counters_t* ctr, unsigned long long* 
     kcore_publish(ctr, mirror, sequence_slot, sequence, 0, 0, 0ull, ctr->next_k);
 }
 
+/// Flush a thread's running minimum: one atomic per wavefront.
+__device__ __forceinline__ void kcore_flush_min(unsigned mn, unsigned* next_k) {
+  mn = wave_min(mn);
+  if (lane_id() == 0 && mn != KCORE_NONE)
+    atomicMin(next_k, mn);
+}
+
 __global__ void __launch_bounds__(KCORE_BLOCK)
     kcore_seed_kernel(const int32_t* ap, const int32_t* deg, int32_t n, int32_t k_prev, int32_t k, int32_t* queue,
                       kcore_counters_t* ctr) {
+  const queue_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
   const int lane = lane_id();
   unsigned mn = KCORE_NONE;
   unsigned long long dsum = 0;
   const int64_t stride = (int64_t)gridDim.x * KCORE_BLOCK;
-  // whole wavefronts run every trip: the ballot below sees all 64 lanes
+  // whole wavefronts run every trip: the ballot of queue_append sees all 64 lanes
   for (int64_t v0 = blockIdx.x * (int64_t)KCORE_BLOCK + threadIdx.x - lane; v0 < n; v0 += stride) {
     const int64_t v = v0 + lane;
     bool leave = false;
@@ -128,39 +117,16 @@ __global__ void __launch_bounds__(KCORE_BLOCK)
       if (d > k)
         mn = min(mn, (unsigned)d);
     }
-    const unsigned long long m = __ballot(leave);
-    if (m) {
-      int32_t base = 0;
-      if (lane == 0)
-        base = atomicAdd(&ctr->tail, __popcll(m));
-      base = __shfl(base, 0, wave_size);
-      if (leave) {
-        queue[base + rank_in_mask(m)] = (int32_t)v;
-        dsum += (unsigned long long)(ap[v + 1] - ap[v]);
-      }
-    }
+    queue_append<false>(leave, (int32_t)v, ap, sink, dsum);
   }
-  mn = wave_min(mn);
-  dsum = wave_sum(dsum);
-  if (lane == 0) {
-    if (mn != KCORE_NONE)
-      atomicMin(&ctr->next_k, mn);
-    if (dsum)
-      atomicAdd(&ctr->degsum, dsum);
-  }
+  kcore_flush_min(mn, &ctr->next_k);
+  queue_flush(dsum, &ctr->degsum);
 }
-
-/// Where a peel kernel appends the vertices whose degree crossed k.
-struct kcore_sink_t {
-  int32_t* queue;
-  int* tail;                   // global (wide, big) or LDS (narrow)
-  unsigned long long* degsum;  // likewise
-};
 
 /// One entry w of a removed row (`active` lanes hold one); every lane of the wavefront calls it.
 template <bool NARROW>
 __device__ __forceinline__ void kcore_relax(bool active, int32_t w, int32_t k, const int32_t* ap, int32_t* deg,
-                                            const kcore_sink_t& sink, unsigned& mn, unsigned long long& dsum) {
+                                            const queue_sink_t& sink, unsigned& mn, unsigned long long& dsum) {
   bool cross = false;
   if (active && deg[w] > k) {
     const int32_t old = atomicSub(&deg[w], 1);
@@ -168,22 +134,7 @@ __device__ __forceinline__ void kcore_relax(bool active, int32_t w, int32_t k, c
     if (old - 1 > k)
       mn = min(mn, (unsigned)(old - 1));
   }
-  const unsigned long long m = __ballot(cross);
-  if (m) {
-    const int first = __ffsll((long long)m) - 1;
-    int32_t base = 0;
-    if (lane_id() == first)
-      base = atomicAdd(sink.tail, __popcll(m));
-    base = __shfl(base, first, wave_size);
-    if (cross) {
-      const int32_t at = base + rank_in_mask(m);
-      if (NARROW)  // read back by this workgroup in the next generation: past the L1
-        store_relaxed(sink.queue + at, w);
-      else
-        sink.queue[at] = w;
-      dsum += (unsigned long long)(ap[w + 1] - ap[w]);
-    }
-  }
+  queue_append<NARROW>(cross, w, ap, sink, dsum);
 }
 
 /// Remove queue[a, b) (b - a <= BLOCK) at level k with the whole workgroup.  Returns the entries
@@ -191,56 +142,25 @@ __device__ __forceinline__ void kcore_relax(bool active, int32_t w, int32_t k, c
 template <int BLOCK, bool NARROW>
 __device__ __forceinline__ int32_t kcore_peel_chunk(const int32_t* ap, const int32_t* aj, int32_t* deg, int32_t* core,
                                                     int32_t a, int32_t b, int32_t k, int32_t big_row, int32_t* big,
-                                                    kcore_counters_t* ctr, const kcore_sink_t& sink, int32_t* s_pre,
+                                                    kcore_counters_t* ctr, const queue_sink_t& sink, int32_t* s_pre,
                                                     int32_t* s_base, int32_t* s_wave, unsigned& mn,
                                                     unsigned long long& dsum) {
-  const int tid = threadIdx.x;
-  int32_t lo = 0, d = 0;
-  if (a + tid < b) {
-    const int32_t u = NARROW ? load_relaxed(sink.queue + a + tid) : sink.queue[a + tid];
-    lo = ap[u];
-    d = ap[u + 1] - lo;
-    core[u] = k;
-    if (!NARROW && d > big_row) {
-      big[atomicAdd(&ctr->big_n, 1)] = u;
-      d = 0;
-    }
-  }
-  int32_t P = 0;
-  const int32_t excl = block_exclusive_sum<BLOCK>(d, P, s_wave);
-  s_pre[tid] = excl + d;
-  s_base[tid] = lo - excl;
-  __syncthreads();
-  const int cnt = b - a;
-  for (int32_t t0 = 0; t0 < P; t0 += BLOCK) {
-    const int32_t t = t0 + tid;
-    int32_t w = 0;
-    if (t < P)
-      w = aj[s_base[prefix_owner(s_pre, cnt, t)] + t];
-    kcore_relax<NARROW>(t < P, w, k, ap, deg, sink, mn, dsum);
-  }
-  __syncthreads();  // the next chunk rewrites the prefix
-  return P;
-}
-
-/// Flush a thread's running minimum and degree sum: one atomic pair per wavefront.
-__device__ __forceinline__ void kcore_flush(unsigned mn, unsigned long long dsum, unsigned* next_k,
-                                            unsigned long long* degsum) {
-  mn = wave_min(mn);
-  dsum = wave_sum(dsum);
-  if (lane_id() == 0) {
-    if (mn != KCORE_NONE)
-      atomicMin(next_k, mn);
-    if (dsum)
-      atomicAdd(degsum, dsum);
-  }
+  return queue_walk<BLOCK, NARROW>(
+      ap, sink.queue, a, b, s_pre, s_base, s_wave,
+      [&](int32_t u, int32_t, int32_t& d) {
+        core[u] = k;
+        if (!NARROW)
+          queue_divert_big(u, d, big_row, big, &ctr->big_n);
+      },
+      [&](bool live, int, int32_t e) { kcore_relax<NARROW>(live, live ? aj[e] : 0, k, ap, deg, sink, mn, dsum); });
 }
 
 __global__ void __launch_bounds__(KCORE_BLOCK)
-    kcore_wide_kernel(const int32_t* ap, const int32_t* aj, int32_t* deg, int32_t* core, int32_t* queue, int32_t head,
-                      int32_t tail, int32_t chunk, int32_t k, int32_t big_row, int32_t* big, kcore_counters_t* ctr) {
+    kcore_wide_kernel(const int32_t* ap, const int32_t* aj, int32_t* deg, int32_t* core, int32_t* queue, int32_t n,
+                      int32_t head, int32_t tail, int32_t chunk, int32_t k, int32_t big_row, int32_t* big,
+                      kcore_counters_t* ctr) {
   __shared__ int32_t s_pre[KCORE_BLOCK], s_base[KCORE_BLOCK], s_wave[KCORE_BLOCK / wave_size + 1];
-  const kcore_sink_t sink{queue, &ctr->tail, &ctr->degsum};
+  const queue_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
   unsigned mn = KCORE_NONE;
   unsigned long long dsum = 0, walked = 0;
   for (int64_t a = head + (int64_t)blockIdx.x * chunk; a < tail; a += (int64_t)gridDim.x * chunk) {
@@ -248,16 +168,17 @@ __global__ void __launch_bounds__(KCORE_BLOCK)
     walked += (unsigned long long)kcore_peel_chunk<KCORE_BLOCK, false>(ap, aj, deg, core, (int32_t)a, b, k, big_row, big,
                                                                      ctr, sink, s_pre, s_base, s_wave, mn, dsum);
   }
-  kcore_flush(mn, dsum, &ctr->next_k, &ctr->degsum);
+  kcore_flush_min(mn, &ctr->next_k);
+  queue_flush(dsum, &ctr->degsum);
   if (threadIdx.x == 0 && walked)
     atomicAdd(&ctr->edges, walked);
 }
 
 /// The rows on the big list, each spread over the whole grid.
 __global__ void __launch_bounds__(KCORE_BLOCK)
-    kcore_big_kernel(const int32_t* ap, const int32_t* aj, int32_t* deg, int32_t* queue, int32_t k, const int32_t* big,
-                     kcore_counters_t* ctr) {
-  const kcore_sink_t sink{queue, &ctr->tail, &ctr->degsum};
+    kcore_big_kernel(const int32_t* ap, const int32_t* aj, int32_t* deg, int32_t* queue, int32_t n, int32_t k,
+                     const int32_t* big, kcore_counters_t* ctr) {
+  const queue_sink_t sink{queue, n, &ctr->tail, &ctr->degsum};
   const int32_t rows = ctr->big_n;  // written by the wide kernel before this one; constant here
   unsigned mn = KCORE_NONE;
   unsigned long long dsum = 0, walked = 0;
@@ -270,53 +191,35 @@ __global__ void __launch_bounds__(KCORE_BLOCK)
       kcore_relax<false>(e < hi, e < hi ? aj[e] : 0, k, ap, deg, sink, mn, dsum);
     }
   }
-  kcore_flush(mn, dsum, &ctr->next_k, &ctr->degsum);
+  kcore_flush_min(mn, &ctr->next_k);
+  queue_flush(dsum, &ctr->degsum);
   if (blockIdx.x == 0 && threadIdx.x == 0 && walked)
     atomicAdd(&ctr->edges, walked);
 }
 
 /// One workgroup: generations while they are small, then the hand-off to the host.
 __global__ void __launch_bounds__(KCORE_NARROW_BLOCK)
-    kcore_narrow_kernel(const int32_t* ap, const int32_t* aj, int32_t* deg, int32_t* core, int32_t* queue, int32_t k,
-                        int32_t max_vertices, unsigned long long max_edges, kcore_counters_t* ctr,
+    kcore_narrow_kernel(const int32_t* ap, const int32_t* aj, int32_t* deg, int32_t* core, int32_t* queue, int32_t n,
+                        int32_t k, int32_t max_vertices, unsigned long long max_edges, kcore_counters_t* ctr,
                         unsigned long long* mirror, int sequence_slot, unsigned long long sequence) {
   __shared__ int32_t s_pre[KCORE_NARROW_BLOCK], s_base[KCORE_NARROW_BLOCK], s_wave[KCORE_NARROW_BLOCK / wave_size + 1];
   __shared__ int s_tail;
   __shared__ unsigned s_min;
   __shared__ unsigned long long s_dsum;
-  int32_t head = ctr->head, tail = ctr->tail;
-  unsigned long long degsum = ctr->degsum, walked = 0;
-  if (threadIdx.x == 0) {
-    s_tail = tail;
+  if (threadIdx.x == 0)
     s_min = ctr->next_k;
-    s_dsum = 0;
-  }
-  __syncthreads();
-  const kcore_sink_t sink{queue, &s_tail, &s_dsum};
   unsigned mn = KCORE_NONE;
-  // every trip consumes queue slots, and a vertex is queued once: at most V trips
-  while (tail > head && tail - head <= max_vertices && degsum <= max_edges) {
-    unsigned long long dsum = 0;
-    walked += (unsigned long long)kcore_peel_chunk<KCORE_NARROW_BLOCK, true>(
-        ap, aj, deg, core, head, tail, k, 0, nullptr, ctr, sink, s_pre, s_base, s_wave, mn, dsum);
-    dsum = wave_sum(dsum);
-    if (lane_id() == 0 && dsum)
-      atomicAdd(&s_dsum, dsum);
-    __syncthreads();
-    head = tail;
-    tail = s_tail;
-    degsum = s_dsum;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      s_dsum = 0;  // appends come after the barriers of the next chunk's prefix sum
-  }
-  mn = wave_min(mn);
-  if (lane_id() == 0 && mn != KCORE_NONE)
-    atomicMin(&s_min, mn);
+  const narrow_result_t r = narrow_generations(
+      ctr, queue, n, max_vertices, max_edges, &s_tail, &s_dsum,
+      [&](int32_t head, int32_t tail, const queue_sink_t& sink, unsigned long long& dsum) {
+        return kcore_peel_chunk<KCORE_NARROW_BLOCK, true>(ap, aj, deg, core, head, tail, k, 0, nullptr, ctr, sink, s_pre,
+                                                          s_base, s_wave, mn, dsum);
+      });
+  kcore_flush_min(mn, &s_min);
   __syncthreads();
   if (threadIdx.x == 0) {
-    ctr->edges += walked;  // no other kernel of the call runs beside this one
-    kcore_publish(ctr, mirror, sequence_slot, sequence, head, tail, degsum, s_min);
+    ctr->edges += r.walked;  // no other kernel of the call runs beside this one
+    kcore_publish(ctr, mirror, sequence_slot, sequence, r.head, r.tail, r.degsum, s_min);
   }
 }
 

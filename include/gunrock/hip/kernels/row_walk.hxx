@@ -1,12 +1,12 @@
 /**
  * @file row_walk.hxx
- * @brief What the kernels of the non-traversal algorithms (cc, mst, kcore) share: the stamp that
- * ends a publish kernel, the split of a long row into segments for whole workgroups, and the walk
- * over a chunk's rows flattened across the workgroup's threads.
+ * @brief What the kernels of the non-traversal algorithms (cc, mst, kcore, color) share: the stamp
+ * that ends a publish kernel, the split of a long row into segments for whole workgroups, and the
+ * walk over a chunk's rows flattened across the workgroup's threads.
  *
- * kcore_peel_chunk keeps its own walk: its loop runs whole wavefronts (lanes past the last entry
- * still take part in kcore_relax's ballot) and its big list holds whole rows, so flat_walk and
- * push_big_segments do not fit it without a mode switch.  It shares prefix_owner and stamp_handoff.
+ * flat_walk runs its body for entries only and leaves early when the chunk has none.  A body that
+ * appends to a queue holds a ballot and needs whole wavefronts: that walk is queue_walk
+ * (generation_queue.hxx), whose big list holds whole rows.
  */
 #pragma once
 

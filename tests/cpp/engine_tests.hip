@@ -9,9 +9,10 @@
 #include <gunrock/algorithms/algorithms.hxx>
 #include <gunrock/graph/reorder.hxx>
 #include <gunrock/hip/algorithms.hxx>
-#include <gunrock/hip/kernels/row_walk.hxx>
+#include <gunrock/hip/kernels/generation_queue.hxx>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <numeric>
@@ -79,7 +80,8 @@ struct toy_enactor_t : gunrock::enactor_t<problem_type> {
   void loop(gcuda::multi_context_t&) override {}
 };
 
-// one small kernel per workgroup helper of hip/primitives.hxx and hip/kernels/row_walk.hxx
+// one small kernel per workgroup helper of hip/primitives.hxx, hip/kernels/row_walk.hxx and
+// hip/kernels/generation_queue.hxx
 template <int BLOCK>
 __global__ void __launch_bounds__(BLOCK) block_sum_probe(const unsigned long long* in, unsigned long long* out) {
   __shared__ unsigned long long s_wave[BLOCK / hip::wave_size];
@@ -97,6 +99,52 @@ __global__ void __launch_bounds__(64) prefix_owner_probe(const int* pre, int cnt
 __global__ void __launch_bounds__(64) push_big_probe(int* big_n, int2* big, int v, int d) {
   if (threadIdx.x == 0)
     hip::kernels::push_big_segments<4096>(big_n, big, v, d);
+}
+
+// two wavefronts; thread t appends vertex t when ready[t]
+template <bool NARROW>
+__global__ void __launch_bounds__(128) queue_append_probe(const int* ready, const int* ap, int* queue, int n, int* tail,
+                                                          unsigned long long* degsum) {
+  const hip::kernels::queue_sink_t sink{queue, n, tail, degsum};
+  unsigned long long dsum = 0;
+  hip::kernels::queue_append<NARROW>(ready[threadIdx.x] != 0, (int)threadIdx.x, ap, sink, dsum);
+  hip::kernels::queue_flush(dsum, degsum);
+}
+// queue[0, cnt) as one chunk: visits[e] counts the live calls at position e, owners[e] keeps their owner
+__global__ void __launch_bounds__(256) queue_walk_probe(const int* ap, const int* queue, int cnt, int big_row, int* big,
+                                                        int* big_n, int* visits, int* owners, int* dead, int* entries) {
+  __shared__ int s_pre[256], s_base[256], s_wave[256 / hip::wave_size + 1];
+  const int P = hip::kernels::queue_walk<256, false>(
+      ap, queue, 0, cnt, s_pre, s_base, s_wave,
+      [&](int v, int, int& d) { hip::kernels::queue_divert_big(v, d, big_row, big, big_n); },
+      [&](bool live, int o, int e) {
+        if (live) {
+          atomicAdd(&visits[e], 1);
+          owners[e] = o;
+        } else {
+          atomicAdd(dead, 1);
+        }
+      });
+  if (threadIdx.x == 0)
+    *entries = P;
+}
+// a chain: the generation {v} walks row v and appends v + 1 while there is one
+__global__ void __launch_bounds__(1024) narrow_generations_probe(const hip::kernels::queue_counters_t* ctr, const int* ap,
+                                                                 int* queue, int n, unsigned long long max_edges,
+                                                                 hip::kernels::narrow_result_t* out) {
+  __shared__ int s_tail;
+  __shared__ unsigned long long s_dsum;
+  const auto r = hip::kernels::narrow_generations(
+      ctr, queue, n, 1024, max_edges, &s_tail, &s_dsum,
+      [&](int head, int, const hip::kernels::queue_sink_t& sink, unsigned long long& dsum) {
+        const int v = hip::load_relaxed(sink.queue + head);
+        __syncthreads();  // as behind a walk's prefix sum: the loop's reset of the degree sum is over
+        hip::kernels::queue_append<true>(threadIdx.x == 0 && v + 1 < n, v + 1, ap, sink, dsum);
+        __syncthreads();
+        return ap[v + 1] - ap[v];
+      });
+  if (threadIdx.x == 0)
+    *out = r;
 }
 
 static FILE* dump = nullptr;
@@ -924,6 +972,112 @@ int main(int argc, char** argv) {
     auto pairs = big.to_host();
     pairs.resize(2 * 5);
     CHECK((pairs == std::vector<int>{7, 0, 7, 1, 9, 0, 9, 1, 11, 0}));
+  }
+
+  // ---- the generation queue shared by the kcore / color kernels, each piece against a host loop -----
+  {
+    // append: 128 vertices with row lengths 1..5, a tail that starts at 7, canaries behind the slots
+    std::vector<int> ap(129, 0);
+    for (int v = 0; v < 128; ++v) ap[v + 1] = ap[v] + v % 5 + 1;
+    auto d_ap = upload(ap);
+    const int start = 7, canary = -7;
+    auto check_append = [&](auto narrow_tag, const std::vector<int>& ready, int short_by) {
+      std::vector<int> want;
+      unsigned long long want_degsum = 0;
+      for (int v = 0; v < 128; ++v)
+        if (ready[v]) {
+          want.push_back(v);
+          want_degsum += (unsigned long long)(ap[v + 1] - ap[v]);
+        }
+      const int final_tail = start + (int)want.size(), n = final_tail - short_by;
+      auto d_ready = upload(ready);
+      auto d_queue = upload(std::vector<int>(final_tail + 8, canary));
+      auto d_tail = upload(std::vector<int>{start});
+      auto d_degsum = upload(std::vector<unsigned long long>{0});
+      queue_append_probe<decltype(narrow_tag)::value><<<1, 128, 0, ctx.stream()>>>(
+          d_ready.data(), d_ap.data(), d_queue.data(), n, d_tail.data(), d_degsum.data());
+      ctx.synchronize();
+      CHECK(d_tail.to_host()[0] == final_tail);
+      CHECK(d_degsum.to_host()[0] == want_degsum);
+      const auto q = d_queue.to_host();
+      bool untouched = true;
+      for (int i = 0; i < (int)q.size(); ++i)
+        untouched = untouched && (q[i] == canary || (i >= start && i < n));
+      CHECK(untouched);  // nothing before the tail, nothing at or beyond n
+      std::vector<int> got(q.begin() + start, q.begin() + n);
+      std::sort(got.begin(), got.end());
+      CHECK(std::adjacent_find(got.begin(), got.end()) == got.end());               // each once
+      CHECK(std::includes(want.begin(), want.end(), got.begin(), got.end()));        // only ready vertices
+      CHECK((int)got.size() == (int)want.size() - short_by && got.front() != canary);  // every slot below n
+    };
+    std::vector<int> few(128, 0), all(128, 1);
+    few[5] = few[17] = few[63] = 1;  // wavefront 1 has no ready lane
+    for (const auto& ready : {few, all})
+      for (int short_by : {0, 2}) {
+        check_append(std::false_type(), ready, short_by);
+        check_append(std::true_type(), ready, short_by);
+      }
+
+    // walk: owner i holds vertex order[i]; returns {entries, dead calls, rows on the big list}
+    auto check_walk = [&](const std::vector<int>& owner_lengths, int big_row) {
+      const std::vector<int> order = {4, 2, 0, 3, 1};
+      std::vector<int> lengths(5), wap(6, 0);
+      for (int i = 0; i < 5; ++i) lengths[order[i]] = owner_lengths[i];
+      for (int v = 0; v < 5; ++v) wap[v + 1] = wap[v] + lengths[v];
+      std::vector<int> want_visits(wap[5] + 1, 0), want_owners(wap[5] + 1, -1), want_big;
+      int want_entries = 0;
+      for (int i = 0; i < 5; ++i) {
+        if (owner_lengths[i] > big_row) {
+          want_big.push_back(order[i]);
+          continue;
+        }
+        want_entries += owner_lengths[i];
+        for (int e = wap[order[i]]; e < wap[order[i] + 1]; ++e) {
+          want_visits[e] = 1;
+          want_owners[e] = i;
+        }
+      }
+      auto d_wap = upload(wap);
+      auto d_queue = upload(order);
+      auto d_visits = upload(std::vector<int>(wap[5] + 1, 0));
+      auto d_owners = upload(std::vector<int>(wap[5] + 1, -1));
+      auto d_misc = upload(std::vector<int>{0, 0, -1});  // big_n, dead calls, entries
+      hip::device_array_t<int> d_big(5);
+      queue_walk_probe<<<1, 256, 0, ctx.stream()>>>(d_wap.data(), d_queue.data(), 5, big_row, d_big.data(), d_misc.data(),
+                                                   d_visits.data(), d_owners.data(), d_misc.data() + 1,
+                                                   d_misc.data() + 2);
+      ctx.synchronize();
+      const auto misc = d_misc.to_host();
+      auto on_big = d_big.to_host();
+      on_big.resize(std::min(misc[0], 5));
+      CHECK(d_visits.to_host() == want_visits && d_owners.to_host() == want_owners);
+      CHECK(misc[2] == want_entries && on_big == want_big);
+      CHECK(misc[1] == (want_entries + 255) / 256 * 256 - want_entries);
+      return std::vector<int>{misc[2], misc[1], misc[0]};
+    };
+    // 365 entries: one BLOCK boundary crossed, not a multiple of 64
+    CHECK((check_walk({0, 1, 300, 0, 64}, INT_MAX) == std::vector<int>{365, 2 * 256 - 365, 0}));
+    CHECK((check_walk({0, 0, 0, 0, 0}, INT_MAX) == std::vector<int>{0, 0, 0}));
+    CHECK((check_walk({0, 1, 300, 0, 64}, 100) == std::vector<int>{65, 256 - 65, 1}));  // the long row: listed once, not walked
+
+    // narrow loop: generations {0}, {1}, {2}, {3} of 3, 5, 100 and 7 entries; the third is too large
+    {
+      const std::vector<int> cap = {0, 3, 8, 108, 115};
+      auto d_cap = upload(cap);
+      auto d_queue = upload(std::vector<int>{0, -1, -1, -1});
+      hip::kernels::queue_counters_t c{};
+      c.tail = 1;
+      c.degsum = 3;
+      auto d_ctr = upload(std::vector<hip::kernels::queue_counters_t>{c});
+      hip::device_array_t<hip::kernels::narrow_result_t> d_out(1);
+      narrow_generations_probe<<<1, 1024, 0, ctx.stream()>>>(d_ctr.data(), d_cap.data(), d_queue.data(), 4, 50ull,
+                                                            d_out.data());
+      ctx.synchronize();
+      const auto r = d_out.to_host()[0];
+      CHECK(r.generations == 2 && r.head == 2 && r.tail == 3);  // stopped with the third pending
+      CHECK(r.degsum == 100 && r.walked == 3 + 5);
+      CHECK((d_queue.to_host() == std::vector<int>{0, 1, 2, -1}));
+    }
   }
 
   // ---- unsupported variants throw (reference advance.hxx:121-127) ---------------------------
