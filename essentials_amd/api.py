@@ -214,6 +214,7 @@ _SIGNATURES = {
     "grx_kcore": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_color": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_cc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_scc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_mst": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP,
                           C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
@@ -731,6 +732,28 @@ def cc(ctx: Context, g: Graph, components=None, options: Optional[Options] = Non
     ctx.after_torch()
     _check(load_library().grx_cc(ctx._h, g._h, _ptr(components), C.byref(count), C.byref(o), C.byref(s)),
            "grx_cc")
+    return components, int(count.value), Stats._from(s)
+
+
+def scc(ctx: Context, g: Graph, components=None, options: Optional[Options] = None):
+    """Strongly connected components -> (int32 labels on the device, number of components as an int,
+    Stats).
+
+    labels[v] is the smallest vertex id of the strongly connected component that holds v, the
+    convention of `cc`: labels[v] == v marks a representative, a vertex on no cycle is a component of
+    one.  A directed graph needs its in-edges (`g.build_in_edges(ctx)`); without them a symmetric CSR
+    is answered by `cc` and an asymmetric one raises EngineError.  `components`: int32 contiguous
+    tensor of V on the context's device, allocated when None and filled in place otherwise.
+    Stats.iterations is the number of forward-backward rounds (0 when trimming finished everything),
+    Stats.vertices_reached is V - components and Stats.edges_expanded the row entries of either
+    array read."""
+    components = _vertex_output(ctx, g, components, "scc", "components")
+    count = C.c_int64()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_scc(ctx._h, g._h, _ptr(components), C.byref(count), C.byref(o), C.byref(s)),
+           "grx_scc")
     return components, int(count.value), Stats._from(s)
 
 

@@ -373,6 +373,45 @@ int grx_color(grx_context_t ctx, grx_graph_t g, int32_t* d_colors, int32_t* h_nu
  * releases its workspace when it returns. */
 int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_components,
            const grx_options* opt, grx_stats* stats);
+/* Strongly connected components (no reference counterpart: the reference has no such algorithm).
+ * u and v share a component iff each reaches the other along row entries.  d_component: device
+ * int32[V] out, overwritten; d_component[v] is the SMALLEST VERTEX ID, in the caller's numbering, of
+ * the strongly connected component that holds v: the convention of grx_cc, so the two compose.
+ * Hence d_component[v] <= v, v is its component's representative iff d_component[v] == v, and the
+ * result is a function of the CSR alone: not of the schedule, the pivots, the order of a row's
+ * entries or a hot-first copy.  The same call returns bit-identical values.  Self loops and repeated
+ * entries change nothing; a vertex on no cycle is a component of one.  h_components: HOST out, the
+ * number of components.  At least one of the two must be non-NULL (GRX_ERR_INVALID_ARGUMENT
+ * otherwise); with d_component == NULL the call works on an array of its own.  n_rows != n_cols is
+ * GRX_ERR_INVALID_ARGUMENT; V == 0 is GRX_OK with *h_components = 0 and nothing written.  opt may be
+ * NULL; only collect_kernel_time is read, and max_iterations != 0 is GRX_ERR_INVALID_ARGUMENT.
+ * Which edges: with in-edges attached (grx_graph_build_in_edges) the call walks both arrays.
+ * Without them, when the handle's verdict is "symmetric" (an unknown one is verified first, as
+ * grx_bc and pull PageRank do), every edge runs both ways and the answer is grx_cc's: the call
+ * returns grx_cc on the same arguments, stats included.  Without in-edges and asymmetric:
+ * GRX_ERR_UNSUPPORTED, and the message names grx_graph_build_in_edges.
+ * Method: forward-backward with trimming, all regions at once, on the generation queue of
+ * grx_kcore.  A region is a set of unfinished vertices known to be a union of whole components (at
+ * the start: everything); an entry is alive when it is no self loop and both ends are unfinished and
+ * in one region.  Trimming: a vertex without an alive out-entry or in-entry is a component of one;
+ * it leaves, its rows lower its neighbours' counts, and whoever reaches 0 follows.  A round: every
+ * region picks the vertex of largest key(v) = (min(alive_out(v) * alive_in(v), 2^32 - 1) << 32) |
+ * fmix32(v) as its pivot (fmix32: grx_color's hash), the pivots' forward reach FW over the out-rows
+ * and backward reach BW over the in-rows are marked, FW n BW is the pivot's component and FW \ BW,
+ * BW \ FW and the rest are the regions of the next round, which are counted and trimmed again.
+ * Rows above GRX_SCC_BIG_ROW entries (default 4096) are walked by the whole grid; generations of at
+ * most 1024 vertices and GRX_SCC_NARROW_EDGES entries (default 16384; 0 = never) run inside one
+ * workgroup without the host; GRX_SCC_TRIM = 0 switches trimming off (singletons are then found as
+ * pivots; for tests).  More than V rounds is GRX_ERR_RUNTIME.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels, batch by
+ * batch, when collect_kernel_time is set), advance_launches (kernel launches), iterations (the
+ * forward-backward rounds run -- defined by the schedule; 0 when trimming finished everything),
+ * vertices_reached (V - components), edges_traversed = edges_expanded (row entries of either array
+ * read by the counting, trimming and reach kernels: at most 2 * nnz * (2 * iterations + 2)).  The
+ * call runs on the caller's CSR as given, builds and uses no hot-first copy, leaves nothing on the
+ * handle but the symmetry verdict and releases its workspace when it returns. */
+int grx_scc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_components,
+            const grx_options* opt, grx_stats* stats);
 /* Minimum spanning FOREST of the CSR as given (the reference's mst.hxx returns one float total,
  * accumulated by float atomics, on connected graphs only, and no edges; this is not a port of it).
  * Every row entry e = (u, v, w) is an undirected candidate edge, whatever its direction; e is the

@@ -63,18 +63,8 @@ struct color_counters_t : queue_counters_t {
 /// The mirror words the host reads per hand-off besides the queue's.
 enum { CL_MAX_COLOR = GQ_WORDS, CL_GENERATIONS, CL_WORDS };
 
-/// The 32-bit finaliser: a bijection on the unsigned vertex id.
-__host__ __device__ __forceinline__ unsigned color_fmix32(unsigned h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
-
 __device__ __forceinline__ unsigned long long color_key(const int32_t* ap, int32_t v) {
-  return ((unsigned long long)(unsigned)(ap[v + 1] - ap[v]) << 32) | color_fmix32((unsigned)v);
+  return ((unsigned long long)(unsigned)(ap[v + 1] - ap[v]) << 32) | fmix32((unsigned)v);
 }
 
 /// One entry naming a vertex w that the row's vertex precedes (`down` lanes hold one): one
@@ -182,7 +172,7 @@ __device__ __forceinline__ int32_t color_chunk(const int32_t* ap, const int32_t*
   const int32_t P = queue_walk<BLOCK, NARROW>(
       ap, sink.queue, a, b, s.pre, s.base, s.wave,
       [&](int32_t u, int32_t, int32_t& d) {
-        s.key[tid] = ((unsigned long long)(unsigned)d << 32) | color_fmix32((unsigned)u);
+        s.key[tid] = ((unsigned long long)(unsigned)d << 32) | fmix32((unsigned)u);
         if (NARROW || !queue_divert_big(u, d, big_row, big, &ctr->big_n))
           v = u;
         s.vert[tid] = v;
@@ -255,7 +245,7 @@ __global__ void __launch_bounds__(COLOR_BLOCK)
     if (v < n) {
       lo = ap[v];
       d = max(ap[v + 1] - lo, 0);
-      kv = ((unsigned long long)(unsigned)d << 32) | color_fmix32((unsigned)v);
+      kv = ((unsigned long long)(unsigned)d << 32) | fmix32((unsigned)v);
       rows += d > 0;
       mxrow = max(mxrow, (unsigned)d);
       if (d > big_row) {

@@ -23,6 +23,16 @@ __device__ __forceinline__ void stamp_handoff(unsigned long long* mirror, int se
   __hip_atomic_store(&mirror[sequence_slot], sequence, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+/// The 32-bit finaliser: a bijection on the unsigned vertex id (the tie-break of color's and scc's keys).
+__host__ __device__ __forceinline__ unsigned fmix32(unsigned h) {
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
 /// Put the d entries of row v on the big list as ceil(d / SEGMENT) items {v, segment}.
 template <int SEGMENT>
 __device__ __forceinline__ void push_big_segments(int* big_n, int2* big, int32_t v, int32_t d) {
