@@ -2,7 +2,7 @@
  * @file capi_batch.hxx
  * @brief Host scaffold of the calls that are batches of their own kernels rather than operator
  * pipelines (grx_tc, grx_kcore, grx_cc, grx_mst, grx_color; grx_bc takes the grid and the clock):
- * test hooks, grid sizing, the call's clock, the hand-off that ends a batch, the symmetric-CSR gate,
+ * grid sizing, the call's clock, the hand-off that ends a batch, the symmetric-CSR gate,
  * and what the generation-queue calls (grx_kcore, grx_color) share.  Not installed.
  */
 #pragma once
@@ -16,16 +16,9 @@
 
 namespace essentials_amd {
 
-/// A test hook: the integer in environment variable `name` clamped to [lo, hi]; `fallback` when unset.
-inline long long env_or(const char* name, long long fallback, long long lo, long long hi) {
-  if (const char* e = std::getenv(name))
-    return std::max(lo, std::min(hi, std::atoll(e)));
-  return fallback;
-}
-
 /// Workgroups for `items` at `per_block` each: at least one, at most eight per CU.
 inline unsigned grid_for(std::size_t items, std::size_t per_block, gcuda::standard_context_t& ctx) {
-  return operators::advance::detail::grid_for(items, per_block, (unsigned)ctx.compute_units() * 8u);
+  return hip::grid_for(items, per_block, (unsigned)ctx.compute_units() * 8u);
 }
 
 /// The two clocks of a call: the whole call (grx_stats::elapsed_ms) and, when `timed`
@@ -69,7 +62,7 @@ unsigned long long* hand_off(gcuda::standard_context_t& sc, call_clock_t& clock,
   publish(ws.mirror(), (int)gcuda::workspace_t::sequence_slot, seq);
   GRX_HIP_CHECK(hipGetLastError());
   clock.end_batch();
-  return operators::advance::detail::await_counters(sc, seq);
+  return hip::await_counters(sc, seq);
 }
 
 /// Undirected input only: an attached transpose marks the graph directed, and a graph nobody has

@@ -1,7 +1,7 @@
 /** @file capi_bc.hip  grx_bc == gunrock::bc::run summed over a list of sources (reference
  * algorithms/bc.hxx), deterministic: the sweeps pull (hip/kernels/bc_kernels.hxx). */
 #include "capi_batch.hxx"
-#include "clients.hxx"
+#include "capi_traversal.hxx"
 
 #include <gunrock/hip/kernels/bc_kernels.hxx>
 
@@ -50,10 +50,7 @@ extern "C" int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources
   for (int32_t i = 0; i < n_sources; ++i)
     if (h_sources[i] < 0 || h_sources[i] >= g->n_rows)
       return invalid("grx_bc: source out of range");
-  grx_options o;
-  grx_default_options(&o);
-  if (opt)
-    o = *opt;
+  grx_options o = effective_options(opt);
   if (o.max_iterations != 0)
     return invalid("grx_bc: max_iterations must be 0 (a truncated search gives wrong centralities)");
   return guarded([&] {
@@ -69,15 +66,12 @@ extern "C" int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources
       // depths, sweeps and sums run on the hot-first copy when grx_bfs would (a directed graph
       // with attached in-edges keeps the caller's numbering: hot_copy says no); bc is delivered
       // in the caller's numbering once, at the end
-      grx_graph_s* run_on = g;
-      if (!o.call_every_edge && !o.holes_layout)
-        if (grx_graph_s* h = hot_copy(ctx, g))
-          run_on = h;
-      const bool renumbered = run_on != g;
-      graph_type G = run_on->view();
+      const run_graph_t run = run_graph(ctx, g, !o.call_every_edge && !o.holes_layout);
+      const bool renumbered = run.renumbered();
+      graph_type G = run.on->view();
       const auto in = G.in_edges();
-      const int32_t* ap = run_on->d_ap;
-      const int32_t* aj = run_on->d_aj;
+      const int32_t* ap = run.on->d_ap;
+      const int32_t* aj = run.on->d_aj;
       const int32_t* in_ap = in.get_row_offsets();
       const int32_t* in_aj = in.get_column_indices();
       const int32_t n = g->n_rows;
@@ -120,37 +114,15 @@ extern "C" int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources
       }
       hip::device_array_t<unsigned char> temp(std::max<std::size_t>(256, std::max(sort_bytes, scan_bytes)));
 
-      enactor_properties_t props;
-      if (o.frontier_sizing_factor > 0)
-        props.frontier_sizing_factor = o.frontier_sizing_factor;
       std::vector<int32_t> h_bounds;
       unsigned long long h_counters[2];
       long long levels_total = 0, reached_total = 0, edges_total = 0;
 
       for (int32_t i = 0; i < count; ++i) {
         const int32_t source = h_sources ? h_sources[i] : i;
-        const int32_t src = renumbered ? g->hot_rank_of[(std::size_t)source] : source;
-        // 1. depths: the BFS client, in the numbering it runs in
-        problem_type problem(G, src, depth.data(), ctx->mc);
-        if (!o.direction_optimized) {
-          problem.byte_labels = n > (1 << 22);
-          if (const char* e = std::getenv("GRX_BFS_BYTE_LABELS"))
-            problem.byte_labels = std::atoi(e) != 0;
-        }
-        problem.init();
-        problem.reset();
-        int iterations = 0;
-        if (o.direction_optimized) {
-          clients::bfs_do_enactor_t<problem_type, lb> enactor(&problem, ctx->mc, props);
-          if (o.do_alpha > 0) enactor.alpha = o.do_alpha;
-          if (o.do_beta > 0) enactor.beta = o.do_beta;
-          enactor.enact();
-          iterations = enactor.iteration;
-        } else {
-          clients::bfs_enactor_t<problem_type, lb> enactor(&problem, ctx->mc, props);
-          enactor.enact();
-          iterations = enactor.iteration;
-        }
+        // 1. depths: the BFS client, in the numbering it runs in (max_iterations is 0: checked above)
+        problem_type problem(G, run.vertex(source), depth.data(), ctx->mc);
+        const int iterations = run_bfs_client<lb>(problem, n, o, ctx).iterations;
         levels_total += iterations;
 
         // 2. level lists: reached vertices stably sorted by depth (on the hot-first copy each

@@ -14,6 +14,7 @@
 
 #include <gunrock/algorithms/algorithms.hxx>
 #include <gunrock/hip/algorithms.hxx>
+#include <gunrock/hip/hand_off.hxx>
 
 #include "../../include/essentials_amd.h"
 
@@ -165,6 +166,25 @@ struct grx_graph_s {
 
 namespace essentials_amd {
 
+/// A test hook: the integer in environment variable `name` clamped to [lo, hi]; `fallback` when unset.
+inline long long env_or(const char* name, long long fallback, long long lo, long long hi) {
+  if (const char* e = std::getenv(name))
+    return std::max(lo, std::min(hi, std::atoll(e)));
+  return fallback;
+}
+/// ... and a switch: any integer but 0 turns it on; `fallback` when unset.
+inline bool env_flag(const char* name, bool fallback) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) != 0 : fallback;
+}
+
+/// The options a call runs with: the defaults overlaid by the caller's.
+inline grx_options effective_options(const grx_options* opt) {
+  grx_options o;
+  grx_default_options(&o);
+  return opt ? *opt : o;
+}
+
 /// Apply grx_options to the context for the duration of a call.
 struct scoped_options {
   gcuda::standard_context_t& ctx;
@@ -269,7 +289,7 @@ long long reach_stats(grx_graph_s* g, const label_t* d_labels, label_t unreached
   reach_stats_kernel<label_t><<<grid ? grid : 1, REACH_BLOCK, 0, ctx.stream()>>>(d_labels, unreached, g->d_ap, n, source,
                                                                  ctx.workspace().counters());
   GRX_HIP_CHECK(hipGetLastError());
-  unsigned long long* m = operators::advance::detail::fetch_counters(ctx);
+  unsigned long long* m = hip::fetch_counters(ctx);
   stats->vertices_reached = (int64_t)m[hip::kernels::C_OUT];
   stats->edges_traversed = (int64_t)m[hip::kernels::C_WORK];
   return (long long)m[hip::kernels::C_SELECT];

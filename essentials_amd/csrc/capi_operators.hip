@@ -114,10 +114,7 @@ int grx_advance(grx_context_t ctx, grx_graph_t g, const grx_options* opt, int32_
     return invalid("grx_advance: this edge_op needs d_state");
   if (d_input && n_input < 0)
     return invalid("grx_advance: negative n_input");
-  grx_options o;
-  grx_default_options(&o);
-  if (opt)
-    o = *opt;
+  grx_options o = effective_options(opt);
   return guarded([&] {
     return with_load_balance(o.load_balance, [&](auto lb_tag) -> int {
       constexpr auto lb = decltype(lb_tag)::value;

@@ -1,6 +1,5 @@
 /** @file capi_pr.hip  grx_pagerank == gunrock::pr::run (reference algorithms/pr.hxx:182-216). */
-#include "capi_internal.hxx"
-#include "clients.hxx"
+#include "capi_traversal.hxx"
 
 using namespace essentials_amd;
 
@@ -8,10 +7,7 @@ extern "C" int grx_pagerank(grx_context_t ctx, grx_graph_t g, float alpha, float
                             const grx_options* opt, grx_stats* stats) {
   if (!ctx || !g || !d_p)
     return invalid("grx_pagerank: NULL argument");
-  grx_options o;
-  grx_default_options(&o);
-  if (opt)
-    o = *opt;
+  grx_options o = effective_options(opt);
   if (o.holes_layout)
     o.holes_layout = 0;  // no output frontier
   return guarded([&] {
@@ -26,23 +22,17 @@ extern "C" int grx_pagerank(grx_context_t ctx, grx_graph_t g, float alpha, float
       // both forms run on the hot-first renumbered copy of the graph (reorder.hxx) when it is large
       // enough for the walk over the destination-sorted edge list (operators/by_destination.hxx:
       // that walk needs out-edges only) and hand the ranks over in the caller's numbering
-      grx_graph_s* run_on = g;
       const unsigned long long walk_from = ctx->single().options().by_destination_min_edges;
-      if (walk_from && (unsigned long long)g->nnz >= walk_from)
-        if (grx_graph_s* h = hot_copy(ctx, g, /*csr_only=*/true))
-          run_on = h;
-      if (const char* e = std::getenv("GRX_PR_HOT_FIRST"))
-        if (std::atoi(e) == 0)
-          run_on = g;
-      bool pull_walk = true;  // GRX_PR_PULL_WALK=0: round 2's per-destination lists (they need the transpose)
-      if (const char* e = std::getenv("GRX_PR_PULL_WALK"))
-        pull_walk = std::atoi(e) != 0;
-      if (o.direction_optimized && !pull_walk)
-        run_on = g;
-      graph_type G = run_on->view();
+      // GRX_PR_PULL_WALK=0: round 2's per-destination lists (they need the transpose)
+      const bool pull_walk = env_flag("GRX_PR_PULL_WALK", true);
+      const run_graph_t run = run_graph(ctx, g,
+                                        walk_from && (unsigned long long)g->nnz >= walk_from &&
+                                            env_flag("GRX_PR_HOT_FIRST", true) &&
+                                            !(o.direction_optimized && !pull_walk),
+                                        /*csr_only=*/true);
+      graph_type G = run.on->view();
       problem_type problem(G, alpha, tol, d_p, ctx->mc);
-      if (run_on != g)
-        problem.gather_from = g->hot_rank_of_device.data();
+      problem.gather_from = run.gather_from;
       problem.pull = o.direction_optimized != 0;
       problem.init();
       problem.reset();
@@ -63,11 +53,7 @@ extern "C" int grx_pagerank(grx_context_t ctx, grx_graph_t g, float alpha, float
         iterations = enactor.iteration;
       }
       if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->elapsed_ms = ms;
-        stats->iterations = iterations;
-        stats->advance_kernel_ms = ctx->single().kernel_clock().total_ms;
-        stats->advance_launches = ctx->single().kernel_clock().launches;
+        run_stats(stats, ms, iterations, ctx->single());
         stats->vertices_reached = g->n_rows;
         stats->edges_traversed = (int64_t)g->nnz * iterations;
         stats->pull_iterations = problem.pull ? iterations : 0;
@@ -88,10 +74,7 @@ extern "C" int grx_pagerank_partitioned_scatter(grx_context_t ctx, grx_graph_t l
   if (!ctx || !local || !d_rank || !d_scale || !d_partial || row_begin < 0 || row_end < row_begin ||
       row_end > local->n_rows)
     return invalid("grx_pagerank_partitioned_scatter: bad arguments");
-  grx_options o;
-  grx_default_options(&o);
-  if (opt)
-    o = *opt;
+  grx_options o = effective_options(opt);
   o.holes_layout = 0;
   return guarded([&] {
     return with_load_balance(o.load_balance, [&](auto lb_tag) -> int {

@@ -221,7 +221,7 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
         !ctx->options().holes_layout && work != frontier_t::unknown_work &&
         work >= ctx->options().settled_min_work) {
       {  // part of this level's advance: timed with it when kernels are timed
-        operators::advance::detail::clocked_t clock(*ctx);
+        hip::clocked_t clock(*ctx);
         settled.refresh((std::size_t)G.get_number_of_vertices(), has_depth, *ctx);
         clock.stop();
       }
@@ -864,7 +864,7 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
             work >= ctx->options().settled_min_work) {
           const bool snapshot = !P->bounds_fresh;
           if (snapshot) {  // part of this iteration's advance: timed with it when kernels are timed
-            operators::advance::detail::clocked_t clock(*ctx);
+            hip::clocked_t clock(*ctx);
             P->snapshot_bounds();
             clock.stop();
           }

@@ -211,8 +211,8 @@ int expand_as(grx_context_t ctx, grx_graph_t local, const grx_options& o, int32_
       GRX_HIP_CHECK(hipGetLastError());
     }
     // the hand-off also leaves the pair count in the slot's header word
-    unsigned long long* m = operators::advance::detail::await_counters(
-        sc, operators::advance::detail::publish_counters(sc, reinterpret_cast<long long*>(d_send),
+    unsigned long long* m = hip::await_counters(
+        sc, hip::publish_counters(sc, reinterpret_cast<long long*>(d_send),
                                                          hip::kernels::C_SELECT));
     error::throw_if_exception(m[hip::kernels::C_OVERFLOW] != 0,
                               "grx_partitioned_expand: send buffer too small (needs V + 1 words)");
@@ -324,10 +324,7 @@ int grx_partitioned_expand(grx_context_t ctx, grx_graph_t local, const grx_optio
     return invalid("grx_partitioned_expand: bad arguments");
   if (edge_op != GRX_OP_BFS && edge_op != GRX_OP_SSSP)
     return unsupported("grx_partitioned_expand: edge_op must be GRX_OP_BFS or GRX_OP_SSSP");
-  grx_options o;
-  grx_default_options(&o);
-  if (opt)
-    o = *opt;
+  grx_options o = effective_options(opt);
   return guarded([&] {
     if (edge_op == GRX_OP_BFS)
       return expand_as<int32_t>(ctx, local, o, edge_op, (int32_t*)d_labels, iparam, d_frontier,
@@ -428,7 +425,7 @@ int grx_partitioned_admit(grx_context_t ctx, int32_t edge_op, void* d_labels, in
     enqueue_admit(sc, edge_op, recv_format, d_labels, n_vertices, d_stamp, round, d_recv, world, slot,
                   me, lo, hi, d_next, next_capacity, counters + hip::kernels::C_OUT,
                   counters + hip::kernels::C_OVERFLOW);
-    unsigned long long* m = operators::advance::detail::fetch_counters(sc);
+    unsigned long long* m = hip::fetch_counters(sc);
     error::throw_if_exception(m[hip::kernels::C_OVERFLOW] != 0,
                               "grx_partitioned_admit: next frontier capacity exceeded");
     *n_next = (int64_t)m[hip::kernels::C_OUT];
@@ -455,10 +452,7 @@ int grx_partitioned_step(grx_context_t ctx, grx_graph_t local, const grx_options
   if (d_recv)
     if (int rc = check_recv(edge_op, recv_format, local->n_rows, slot))
       return rc;
-  grx_options o;
-  grx_default_options(&o);
-  if (opt)
-    o = *opt;
+  grx_options o = effective_options(opt);
   return guarded([&] {
     auto& sc = ctx->single();
     auto& ws = sc.workspace();
@@ -469,7 +463,7 @@ int grx_partitioned_step(grx_context_t ctx, grx_graph_t local, const grx_options
     // the previous step's hand-off has long landed (the host synchronised on the gather since):
     // check that nothing overflowed
     if (ctx->pending_sequence) {
-      unsigned long long* m = operators::advance::detail::await_counters(sc, ctx->pending_sequence);
+      unsigned long long* m = hip::await_counters(sc, ctx->pending_sequence);
       ctx->pending_sequence = 0;
       error::throw_if_exception(m[hip::kernels::C_OVERFLOW] != 0,
                                 "grx_partitioned_step: a buffer of the previous superstep overflowed");
@@ -588,7 +582,7 @@ int grx_partitioned_step(grx_context_t ctx, grx_graph_t local, const grx_options
     // 4. hand the counters over (overflow flag), write the pair count into the slot's header, clear
     //    the counters and the frontier length (the next admit accumulates into it) -- one launch,
     //    nobody waits here
-    ctx->pending_sequence = operators::advance::detail::publish_counters(
+    ctx->pending_sequence = hip::publish_counters(
         sc, reinterpret_cast<long long*>(d_send), hip::kernels::C_SELECT, count_dev);
     return (int)GRX_OK;
   });

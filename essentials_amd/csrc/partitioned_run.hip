@@ -311,7 +311,7 @@ int run_as(grx_partitioned_s& p, int32_t edge_op, int32_t source, label_t* calle
   const auto t1 = std::chrono::steady_clock::now();
   // the last step's hand-off has landed: report a buffer overflow of that step here
   if (p.ctx->pending_sequence) {
-    unsigned long long* m = operators::advance::detail::await_counters(sc, p.ctx->pending_sequence);
+    unsigned long long* m = hip::await_counters(sc, p.ctx->pending_sequence);
     p.ctx->pending_sequence = 0;
     error::throw_if_exception(m[hip::kernels::C_OVERFLOW] != 0,
                               "grx_partitioned_run: a buffer of the last superstep overflowed");
@@ -537,7 +537,7 @@ int grx_partitioned_pagerank(grx_partitioned_t plan, float alpha, float tol, int
                                                        1.0f - alpha,
                                                        counters + hip::kernels::C_SELECT);
       GRX_HIP_CHECK(hipGetLastError());
-      unsigned long long* m = operators::advance::detail::fetch_counters(sc);
+      unsigned long long* m = hip::fetch_counters(sc);
       const unsigned bits = (unsigned)m[hip::kernels::C_SELECT];
       std::memcpy(&err, &bits, 4);
       ++it;

@@ -21,6 +21,7 @@
 #include <gunrock/framework/operators/advance.hxx>
 #include <gunrock/framework/operators/configs.hxx>
 #include <gunrock/hip/context.hxx>
+#include <gunrock/hip/hand_off.hxx>
 #include <gunrock/hip/kernels/advance_kernels.hxx>
 #include <gunrock/hip/kernels/compact_kernels.hxx>
 
@@ -166,7 +167,7 @@ void select_range(graph_t& G, std::size_t n, pred_t pred, frontier_t& output,
   constexpr int items = narrow_claims ? k::SEL_ITEMS_NARROW : k::SEL_ITEMS_WIDE;
   const std::size_t chunks = (n_visit + (std::size_t)k::SEL_BLOCK * items - 1) / ((std::size_t)k::SEL_BLOCK * items);
   const std::size_t cap = (std::size_t)context.compute_units() * 2;
-  operators::advance::detail::clocked_t clock(context);  // it IS a level's output path: timed with the advances
+  hip::clocked_t clock(context);  // it IS a level's output path: timed with the advances
   k::select_range_kernel<vertex_t, items><<<(unsigned)(chunks < cap ? chunks : cap), k::SEL_BLOCK, 0,
                                      context.stream()>>>(G, n_visit, pred, output.data(), output.get_capacity(),
                                                          context.workspace().counters(), (int)k::C_OUT,
@@ -174,7 +175,7 @@ void select_range(graph_t& G, std::size_t n, pred_t pred, frontier_t& output,
                                                          bit_words, bit_limit);
   GRX_HIP_CHECK(hipGetLastError());
   clock.stop();
-  unsigned long long* m = operators::advance::detail::fetch_counters(context);
+  unsigned long long* m = hip::fetch_counters(context);
   context.kernel_clock().collect();
   error::throw_if_exception(m[k::C_OVERFLOW] != 0, "select_range: output frontier capacity exceeded");
   output.set_number_of_elements((std::size_t)m[k::C_OUT]);

@@ -39,6 +39,7 @@
 #include <gunrock/framework/operators/advance.hxx>
 #include <gunrock/hip/algorithms.hxx>
 #include <gunrock/hip/context.hxx>
+#include <gunrock/hip/hand_off.hxx>
 #include <gunrock/hip/kernels/exchange_kernels.hxx>
 
 namespace gunrock {
@@ -128,8 +129,8 @@ unsigned long long exchange(frontier_t& found, frontier_t& next, label_t* labels
     GRX_HIP_CHECK(hipGetLastError());
   }
   {
-    unsigned long long* m = operators::advance::detail::await_counters(
-        sc, operators::advance::detail::publish_counters(sc, reinterpret_cast<long long*>(st.send.data()),
+    unsigned long long* m = hip::await_counters(
+        sc, hip::publish_counters(sc, reinterpret_cast<long long*>(st.send.data()),
                                                          k::C_SELECT));
     error::throw_if_exception(m[k::C_OVERFLOW] != 0, "partitioned exchange: send slot overflow");
     packed = (int64_t)m[k::C_SELECT];
@@ -172,7 +173,7 @@ unsigned long long exchange(frontier_t& found, frontier_t& next, label_t* labels
       reinterpret_cast<int32_t*>(next.data()), (unsigned long long)next.get_capacity(),
       counters + k::C_OUT, counters + k::C_OVERFLOW);
   GRX_HIP_CHECK(hipGetLastError());
-  unsigned long long* m = operators::advance::detail::fetch_counters(sc);
+  unsigned long long* m = hip::fetch_counters(sc);
   error::throw_if_exception(m[k::C_OVERFLOW] != 0, "partitioned exchange: next frontier overflow");
   next.set_number_of_elements((std::size_t)m[k::C_OUT]);  // work hint unknown: the advance sizes itself
   ++st.round;

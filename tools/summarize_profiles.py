@@ -33,7 +33,7 @@ def one(pattern):
 
 
 ADVANCE = ("block_mapped_kernel", "chunk_kernel", "classify_hubs_kernel", "expand_fused_kernel",
-           "expand_settled_kernel", "rebuild_kernel", "wave_chunk_kernel", "pull_probe_kernel",
+           "expand_settled_kernel", "rebuild_kernel", "pull_probe_kernel",
            "pull_long_kernel", "select_range_kernel")
 
 
