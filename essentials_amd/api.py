@@ -217,6 +217,7 @@ _SIGNATURES = {
     "grx_scc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_mst": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP,
                           C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_spgemm": (C.c_int, [_VP, _VP, _VP, C.POINTER(_VP), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -780,6 +781,26 @@ def mst(ctx: Context, g: Graph, entries=None, components=None, options: Optional
     _check(load_library().grx_mst(ctx._h, g._h, _ptr(entries), C.byref(count), C.byref(weight),
                                   _ptr(components), C.byref(o), C.byref(s)), "grx_mst")
     return entries[: count.value], float(weight.value), components, Stats._from(s)
+
+
+def spgemm(ctx: Context, a: Graph, b: Graph, options: Optional[Options] = None):
+    """Sparse matrix product C = A * B -> (Graph, Stats): a new owning graph of a.n_rows x b.n_cols.
+
+    C has an entry (i, j) iff some entry (i, k) of A meets an entry (k, j) of B; each is stored once,
+    rows sorted by column, and an entry whose products cancel stays with value 0.0.  Values are
+    float32 sums in an order the call does not promise: exact and the same on every call when the
+    partial sums are representable (integer weights, sum |products| < 2**24 per entry), within the
+    summation bound of the float64 sum otherwise (include/essentials_amd.h).  `a is b` is allowed.
+    More than 2**31 - 1 entries raise EngineError (-3).  Stats.edges_expanded is the number of
+    products, Stats.edges_traversed nnz(C), Stats.vertices_reached the rows of C with an entry; with
+    collect_kernel_time Stats.frontier_slots holds the microseconds of the bound, symbolic and
+    numeric batches."""
+    h = _VP()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_spgemm(ctx._h, a._h, b._h, C.byref(h), C.byref(o), C.byref(s)), "grx_spgemm")
+    return Graph(h), Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

@@ -455,6 +455,50 @@ int grx_scc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_c
  * returns. */
 int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int64_t* h_count, double* h_weight,
             int32_t* d_component, const grx_options* opt, grx_stats* stats);
+/* Sparse matrix product C = A * B as a NEW handle (no counterpart in the reference that could be
+ * ported: its algorithms/spgemm.hxx places entry (m, n) at row_offsets[m] + n, a column id used as a
+ * position inside a row).  *out receives an OWNING handle of shape a.n_rows x b.n_cols that the
+ * caller destroys with grx_graph_destroy and that is an ordinary handle for every other call.
+ * a == b is allowed; in-edges or a hot-first copy attached to a or b are ignored; a and b are not
+ * changed.  C carries no symmetry verdict (unknown), no hot-first copy and no in-edges.
+ * Pattern: C has an entry (i, j) iff there is at least one pair of entries (i, k) in row i of A and
+ * (k, j) in row k of B.  Each (i, j) is stored ONCE, rows are sorted by ascending column, diagonal
+ * entries are kept, and an entry whose products cancel to 0.0 is still an entry: the pattern is
+ * structural, a function of the two index arrays alone -- not of the values, the order of a row's
+ * entries or the schedule.  Repeated entries of A or B each contribute a product, so a multigraph's
+ * multiplicities multiply.
+ * Values: C[i,j] is the float32 sum of A[i,k] * B[k,j] over all such pairs (each product rounded
+ * once), added in an order the call does NOT promise: the sums are LDS float adds that arrive in
+ * schedule order.  The value is exact, and bit-identical from call to call, whenever every partial
+ * sum of those products in any order is representable in float32 -- integer weights with
+ * sum |products| < 2^24 per entry, for one.  Otherwise it lies within the standard summation bound
+ * of the float64 sum and may differ in the last bits between calls; a reproducible ordered sum is
+ * not offered.
+ * Sizes: products are counted in 64 bits.  A handle holds at most INT32_MAX entries: when nnz(C)
+ * exceeds that the call returns GRX_ERR_UNSUPPORTED, the message names the count, and nothing of
+ * that size has been allocated.  a.n_rows == 0, b.n_cols == 0 and operands without entries are
+ * valid and give a handle with empty rows.
+ * Errors: GRX_ERR_INVALID_ARGUMENT for NULL ctx, a, b or out, for a.n_cols != b.n_rows and for
+ * opt->max_iterations != 0.  opt may be NULL; only collect_kernel_time is read.
+ * Method: two-phase Gustavson.  One pass counts the products u(i) of every row.  The symbolic phase
+ * bins the rows by min(u(i), b.n_cols) and counts each row's distinct columns in a hash table in
+ * LDS (open addressing, atomicCAS on the key, load factor <= 1/2): 8 lanes per row for rows of at
+ * most GRX_SPGEMM_SMALL_PRODUCTS products (default and most 32, 0 = never), a wavefront per row up
+ * to 256 entries, a workgroup per row above that, its table sized from the device's LDS per
+ * workgroup.  A 64-bit sum of the counts decides the refusal, a 32-bit scan gives C's row offsets.
+ * The numeric phase bins the rows again by their EXACT length, accumulates a float beside each key
+ * by LDS float adds, sorts the table in place (bitonic, by column) and writes the row.  Rows that
+ * no table holds are walked once per TILE of columns, the tile a bitmap (and a float per column)
+ * in LDS, read out in column order; there are no float atomics to global memory anywhere.
+ * GRX_SPGEMM_LDS_SLOTS lowers the table capacity (and the tile with it): a test hook.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels alone, batch
+ * by batch, when collect_kernel_time is set; 0 otherwise), advance_launches (kernel launches),
+ * iterations (1), vertices_reached (rows of C with an entry), edges_traversed (nnz(C)),
+ * edges_expanded (the products, sum over i of sum over k in row i of A of len(row k of B)); with
+ * collect_kernel_time, levels_recorded is 3 and frontier_slots[0..2] hold the MICROSECONDS of the
+ * bound, symbolic and numeric batches.  The workspace is released when the call returns. */
+int grx_spgemm(grx_context_t ctx, grx_graph_t a, grx_graph_t b, grx_graph_t* out, const grx_options* opt,
+               grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
