@@ -218,6 +218,7 @@ _SIGNATURES = {
     "grx_mst": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP,
                           C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_spgemm": (C.c_int, [_VP, _VP, _VP, C.POINTER(_VP), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_truss": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -801,6 +802,41 @@ def spgemm(ctx: Context, a: Graph, b: Graph, options: Optional[Options] = None):
     ctx.after_torch()
     _check(load_library().grx_spgemm(ctx._h, a._h, b._h, C.byref(h), C.byref(o), C.byref(s)), "grx_spgemm")
     return Graph(h), Stats._from(s)
+
+
+def truss(ctx: Context, g: Graph, values=None, options: Optional[Options] = None):
+    """K-truss decomposition of the simple undirected graph under a symmetric CSR -> (int32 trussness
+    per CSR entry on the device, the largest trussness as an int, Stats).
+
+    values[p] is the largest k >= 2 such that the edge entry p names lies in the k-truss, the maximal
+    subgraph whose every edge is in at least k - 2 of its triangles (the convention of
+    networkx.k_truss: an edge in no triangle has 2, every edge of K_n has n).  The k-truss subgraph
+    is `values >= k`.  Self loops and repeated entries are ignored and row order does not matter:
+    both directions and every repeat of an edge carry the same value, a self loop carries 0.
+    `values`: int32 contiguous tensor of g.nnz on the context's device, allocated when None and
+    filled in place otherwise.  The same call returns identical values.  Stats.iterations is the
+    number of distinct values of the answer, Stats.edges_traversed the number m of distinct
+    undirected edges and Stats.edges_expanded the row entries the intersections read; with
+    collect_kernel_time Stats.frontier_slots holds the microseconds of the copy, support and peel
+    phases."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if values is None:
+        values = torch.empty(g.nnz, dtype=torch.int32, device=device)
+    else:
+        if not isinstance(values, torch.Tensor) or values.dtype != torch.int32:
+            raise TypeError("truss: values must be an int32 torch tensor")
+        if values.dim() != 1 or values.numel() != g.nnz or not values.is_contiguous():
+            raise ValueError(f"truss: values must be a contiguous tensor of {g.nnz} elements")
+        if values.device != device:
+            raise ValueError(f"truss: values must live on {device}")
+    largest = C.c_int32()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_truss(ctx._h, g._h, _ptr(values), C.byref(largest), C.byref(o), C.byref(s)),
+           "grx_truss")
+    return values, int(largest.value), Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

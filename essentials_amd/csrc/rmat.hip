@@ -13,6 +13,7 @@
  * column and weight from the emission index -> row offsets by boundary detection.
  */
 #include "capi_internal.hxx"
+#include "simple_csr.hxx"
 
 #include <algorithm>
 
@@ -143,30 +144,6 @@ std::unique_ptr<grx_graph_s> rmat_build(gcuda::standard_context_t& c, unsigned s
 
 }  // namespace essentials_amd
 
-namespace {
-/// key[e] = (row << 32) | col for every edge: rows from the offsets by binary search
-__global__ void __launch_bounds__(256)
-    row_col_keys_kernel(const int* ap, const int* aj, int n_rows, long long nnz,
-                        unsigned long long* keys) {
-  for (long long e = blockIdx.x * 256ll + threadIdx.x; e < nnz; e += (long long)gridDim.x * 256) {
-    int lo = 0, hi = n_rows;  // ap[lo] <= e < ap[hi]
-    while (hi - lo > 1) {
-      const int mid = lo + (hi - lo) / 2;
-      if ((long long)ap[mid] <= e)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    keys[e] = ((unsigned long long)(unsigned)lo << 32) | (unsigned)aj[e];
-  }
-}
-__global__ void __launch_bounds__(256)
-    keys_to_cols_kernel(const unsigned long long* keys, long long nnz, int* aj) {
-  for (long long e = blockIdx.x * 256ll + threadIdx.x; e < nnz; e += (long long)gridDim.x * 256)
-    aj[e] = (int)(unsigned)(keys[e] & 0xffffffffull);
-}
-}  // namespace
-
 extern "C" int grx_graph_sorted_rows(grx_context_t ctx, grx_graph_t g, grx_graph_t* out) {
   if (!ctx || !g || !out)
     return invalid("grx_graph_sorted_rows: NULL argument");
@@ -206,18 +183,6 @@ extern "C" int grx_graph_sorted_rows(grx_context_t ctx, grx_graph_t g, grx_graph
 }
 
 namespace {
-/// 1 where entry e of the (row, column)-sorted keys stays in the simple graph: the first of its
-/// run of repeats, and not a self loop.  e == nnz (the scan's total slot) -> 0.
-struct simple_keep_t {
-  const unsigned long long* keys;
-  long long nnz;
-  __host__ __device__ int operator()(long long e) const {
-    if (e >= nnz)
-      return 0;
-    const unsigned long long key = keys[e];
-    return (unsigned)(key >> 32) != (unsigned)key && (e == 0 || keys[e - 1] != key);
-  }
-};
 /// Kept entries to their places: column, and the smallest weight of the run of repeats.
 __global__ void __launch_bounds__(256)
     simple_write_kernel(const unsigned long long* keys, const float* ax, const int* at, long long nnz, int* aj_out,
@@ -232,11 +197,6 @@ __global__ void __launch_bounds__(256)
     aj_out[at[e]] = (int)(unsigned)key;
     ax_out[at[e]] = w;
   }
-}
-/// Sorting keeps every row where it was: the new offset of a row is the kept entries before it.
-__global__ void __launch_bounds__(256) simple_offsets_kernel(const int* ap, const int* at, int n_rows, int* ap_out) {
-  for (long long r = blockIdx.x * 256ll + threadIdx.x; r <= n_rows; r += (long long)gridDim.x * 256)
-    ap_out[r] = at[ap[r]];
 }
 }  // namespace
 

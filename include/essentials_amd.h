@@ -499,6 +499,47 @@ int grx_mst(grx_context_t ctx, grx_graph_t g, int32_t* d_entries, int64_t* h_cou
  * bound, symbolic and numeric batches.  The workspace is released when the call returns. */
 int grx_spgemm(grx_context_t ctx, grx_graph_t a, grx_graph_t b, grx_graph_t* out, const grx_options* opt,
                grx_stats* stats);
+/* K-truss decomposition (the reference has none; nothing is ported).
+ * THE TRUSSNESS OF EVERY EDGE of the simple undirected graph under a symmetric CSR.  The input may
+ * be a multigraph with self loops and unsorted rows: as in grx_tc, self loops and repeated entries
+ * are ignored, and the order of a row's entries does not matter.  Let m be the number of distinct
+ * undirected edges that are not self loops.  The k-truss is the largest subgraph in which every
+ * edge lies in at least k - 2 triangles of that subgraph, and truss(e) is the largest k >= 2 whose
+ * k-truss holds e: the convention of networkx.k_truss.  An edge in no triangle has 2, every edge of
+ * the complete graph on n vertices has n.  The k-truss itself is the set of entries with value >= k.
+ * d_truss: device int32[nnz] out, overwritten, ONE VALUE PER CSR ENTRY in the caller's positions
+ * and numbering: entry p = (u, v) carries truss({u, v}), so both directions and every repeat of an
+ * edge carry the same value; a self loop carries 0.  h_max_truss: HOST out, the largest value
+ * written, 0 when there is no edge but self loops (the empty graph included).  At least one of the
+ * two must be non-NULL (GRX_ERR_INVALID_ARGUMENT otherwise).  The result is a function of the CSR
+ * alone and bit-identical from call to call; a hot-first copy on the handle is neither built nor
+ * used.
+ * Undirected input only: n_rows != n_cols is GRX_ERR_INVALID_ARGUMENT; a handle with in-edges
+ * attached, or a CSR that is not its own transpose (verified once when unknown), is
+ * GRX_ERR_UNSUPPORTED.  n_rows == 0 or nnz == 0 is GRX_OK and launches nothing.  opt may be NULL;
+ * only collect_kernel_time is read, and max_iterations != 0 is GRX_ERR_INVALID_ARGUMENT.
+ * Method: the simple copy with sorted rows is built per call, and every edge gets one id, named at
+ * both of its entries.  The support of an edge (its triangles) comes from listing every triangle
+ * once on the degree-oriented copy, as grx_tc does, and adding one to its three edges; rows are
+ * binned by length (8 lanes, a wavefront, a workgroup with the row staged in LDS, or in place when
+ * it does not fit).  The peel works level by level, k = 2, 3, ...: edges with support <= k - 2
+ * leave in generations, each re-intersecting its two rows and lowering the support of the two
+ * other edges of every triangle it was in, never below k - 2.  A triangle that loses two or three
+ * edges in one generation is charged once, by the one with the smallest id, and only to edges
+ * outside that generation: the supports, the generations and so the answer do not depend on
+ * scheduling.  GRX_TRUSS_NARROW_EDGES (the probes a generation
+ * may have to run inside one workgroup; 0 = never) and GRX_TRUSS_LDS_IDS (lowers the staging
+ * capacity) are test hooks.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels, batch by
+ * batch, when collect_kernel_time is set; 0 otherwise), iterations (the levels k at which an edge
+ * left: for m > 0 the number of DISTINCT values of the answer), advance_launches (kernel launches,
+ * a library sort or scan counting as one), edges_traversed (m), edges_expanded (row entries read by
+ * the support pass and the peel's intersections together); with collect_kernel_time,
+ * levels_recorded is 3 and frontier_slots[0..2] hold the MICROSECONDS of building the copy and the
+ * edge ids, of the support pass, and of the peel with the scatter.  The workspace (20 bytes per
+ * entry for the sort, then 48 bytes per edge) is released when the call returns. */
+int grx_truss(grx_context_t ctx, grx_graph_t g, int32_t* d_truss, int32_t* h_max_truss,
+              const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
