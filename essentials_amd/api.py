@@ -219,6 +219,8 @@ _SIGNATURES = {
                           C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_spgemm": (C.c_int, [_VP, _VP, _VP, C.POINTER(_VP), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_truss": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_bfs_multi": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, C.POINTER(_Options),
+                                C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -837,6 +839,60 @@ def truss(ctx: Context, g: Graph, values=None, options: Optional[Options] = None
     _check(load_library().grx_truss(ctx._h, g._h, _ptr(values), C.byref(largest), C.byref(o), C.byref(s)),
            "grx_truss")
     return values, int(largest.value), Stats._from(s)
+
+
+def bfs_multi(ctx: Context, g: Graph, sources=None, depths=None, want_depths: bool = True,
+              options: Optional[Options] = None):
+    """Multi-source BFS, 64 searches to a 64-bit word per vertex -> (int32 depths [count, V] on the
+    device or None, summary, Stats).
+
+    `sources`: None (every vertex), one vertex, or a sequence / numpy array of vertices, as for `bc`;
+    a vertex named twice is searched twice.  Row i of the depths is what `bfs` gives from source i
+    (INT_UNREACHED where unreached).  `depths`: int32 contiguous tensor of count * V elements on the
+    context's device, allocated when None; want_depths=False computes the summaries only (no
+    count * V array exists then) and returns None for the depths.  `summary` is a dict of numpy
+    arrays of count: `reached` (int64, vertices with a finite depth, the source included),
+    `depth_sum` (int64, the sum of the finite depths) and `eccentricity` (int32, the largest one);
+    closeness of source i is (reached[i] - 1) / depth_sum[i].  Options read: collect_kernel_time,
+    direction_optimized and do_alpha.  Stats.iterations is the sum over batches of 64 of 1 + the
+    largest eccentricity in the batch, Stats.edges_traversed the out-degrees of every level's
+    active vertices (the work a batch shares) and Stats.frontier_slots the first batch's levels."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if sources is None:
+        h, n, count = None, 0, g.n_rows
+    else:
+        h = np.ascontiguousarray(np.atleast_1d(np.asarray(sources)), dtype=np.int32)
+        if h.ndim != 1:
+            raise ValueError("bfs_multi: sources must be one vertex or a flat list of vertices")
+        n = count = int(h.size)
+        if n == 0:  # an empty list is not "every vertex": hand the ABI a non-NULL pointer
+            h = np.zeros(1, np.int32)
+    if not want_depths:
+        depths = None
+    elif depths is None:
+        depths = torch.empty((count, g.n_rows), dtype=torch.int32, device=device)
+    else:
+        if not isinstance(depths, torch.Tensor) or depths.dtype != torch.int32:
+            raise TypeError("bfs_multi: depths must be an int32 torch tensor")
+        if depths.numel() != count * g.n_rows or not depths.is_contiguous():
+            raise ValueError(f"bfs_multi: depths must be a contiguous tensor of {count} x {g.n_rows} elements")
+        if depths.device != device:
+            raise ValueError(f"bfs_multi: depths must live on {device}")
+        depths = depths.view(count, g.n_rows)
+    # the host arrays are never NULL, so an empty depths tensor (a NULL pointer) is no argument error
+    reached = np.zeros(max(count, 1), np.int64)
+    depth_sum = np.zeros(max(count, 1), np.int64)
+    eccentricity = np.zeros(max(count, 1), np.int32)
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_bfs_multi(ctx._h, g._h, _ptr(h), n,
+                                        _ptr(depths) if depths is not None and depths.numel() else None,
+                                        _ptr(reached), _ptr(depth_sum), _ptr(eccentricity), C.byref(o), C.byref(s)),
+           "grx_bfs_multi")
+    summary = {"reached": reached[:count], "depth_sum": depth_sum[:count], "eccentricity": eccentricity[:count]}
+    return depths, summary, Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

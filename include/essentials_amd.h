@@ -540,6 +540,64 @@ int grx_spgemm(grx_context_t ctx, grx_graph_t a, grx_graph_t b, grx_graph_t* out
  * entry for the sort, then 48 bytes per edge) is released when the call returns. */
 int grx_truss(grx_context_t ctx, grx_graph_t g, int32_t* d_truss, int32_t* h_max_truss,
               const grx_options* opt, grx_stats* stats);
+/* Multi-source BFS (no reference counterpart): the depths grx_bfs gives, from many sources at once.
+ * h_sources: HOST int32[n_sources] in the caller's numbering; NULL = every vertex 0..V-1 (n_sources
+ * must then be 0): grx_bc's convention.  Let count be the number of searches.  A vertex may appear
+ * more than once: each occurrence is a search of its own, with its own row and summaries.  A non-NULL
+ * list with n_sources == 0, and V == 0, are GRX_OK: no output is written and nothing is launched
+ * (stats, when given, is zeroed all the same).
+ * d_depths: device int32[count * V] out, overwritten, or NULL.  Row i is at elements
+ * [i * V, (i + 1) * V), an index computed in 64 bits (count * V may pass 2^31), and is exactly what
+ * grx_bfs(ctx, g, source_i, ...) writes: hop counts along row entries as given, 0 at the source,
+ * INT32_MAX where unreached.  A directed CSR is walked along its out-entries; self loops and
+ * repeated entries change nothing.  With d_depths == NULL the call computes the summaries only and
+ * allocates no count * V array of its own.
+ * h_reached[i] (HOST int64[count]): the vertices with a finite depth, the source included.
+ * h_depth_sum[i] (HOST int64[count]): the sum of the finite depths.  h_eccentricity[i] (HOST
+ * int32[count]): the largest finite depth.  Each may be NULL; at least one of the four outputs must
+ * be non-NULL.  Closeness of s is (reached - 1) / depth_sum: the caller's arithmetic.
+ * The result is a function of the CSR and the source list alone, bit-identical from call to call,
+ * and does not depend on push, pull or how the sources fall into batches.
+ * Errors, all found on the host before anything is launched: GRX_ERR_INVALID_ARGUMENT for a NULL ctx
+ * or g, n_sources < 0, h_sources == NULL with n_sources != 0, a source out of range, four NULL
+ * outputs, n_rows != n_cols and opt->max_iterations != 0.  With opt->direction_optimized == 1 and a
+ * graph that cannot be pulled (an asymmetric CSR without in-edges; an unknown verdict is verified
+ * first) the call returns what grx_bfs returns: GRX_ERR_UNSUPPORTED.
+ * opt may be NULL; collect_kernel_time, direction_optimized and do_alpha (0: its default, 4) are
+ * read, everything else -- the load-balance choice included -- is ignored.
+ * Method: bit-parallel search ("The More the Merrier", Then et al., VLDB 2014).  The sources are
+ * taken 64 at a time in list order (the last batch may be partial); bit i of a 64-bit word stands for
+ * search i of the batch.  Every vertex has a word `seen` and a word in each of two frontier arrays,
+ * the current level's and the next one's; a level's active list holds every vertex with a non-zero
+ * frontier word once.  A PUSH level walks the active list's rows: entry (u, v) offers
+ * frontier[u] & ~seen[v] & ~next[v] and, when that is not 0, ORs it into next[v] with one 64-bit
+ * atomic; the lane that gets 0 back lists v.  An update pass over the new list makes the words
+ * `seen`, writes depth[i * V + v] for every new bit i and counts, per bit, the vertices reached:
+ * those counts are the three summaries (integer sums: order cannot matter).  With
+ * direction_optimized == 1 a level whose active rows have more than nnz / do_alpha entries is PULLED
+ * instead (chosen per level, no hysteresis): every vertex that still lacks a search ORs the frontier
+ * words of its in-neighbours (the in-edge arrays, or its own row on a symmetric CSR) and stops
+ * reading once nothing is lacking; no atomics.  The default of 4 is grx_bfs's and is not measured
+ * for this kernel.  Rows above GRX_BFSM_BIG_ROW entries (default 4096; a test hook) go to whole
+ * workgroups in either form.  One host hand-off per level.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels, batch by
+ * batch, when collect_kernel_time is set), advance_launches (kernel launches), iterations (the sum
+ * over batches of 1 + the largest eccentricity in the batch: defined by the answer), pull_iterations
+ * (levels expanded by pulling), vertices_reached (the sum of the reached values), edges_traversed
+ * (the sum, over every level of every batch, of the out-degrees of that level's active vertices:
+ * the work a batch shares), edges_expanded (the row entries the expanding kernels actually read.
+ * A pushed level reads every entry of its active rows, so the host adds that level's degree sum
+ * and no kernel counts: the figure equals edges_traversed by construction when every level pushed.
+ * A pulled level counts, on the device, the in-row entries read before its early exits, which
+ * depends on the schedule and may differ between calls -- the answer cannot), levels_recorded (min(levels of the FIRST batch, 64)) and frontier_slots[L] (the vertices
+ * that have depth L for at least one source of the first batch).
+ * The call runs on the caller's CSR as given, builds and uses no hot-first copy, leaves nothing on
+ * the handle but a symmetry verdict ensure_can_pull may have produced, and releases its workspace
+ * when it returns: 32 bytes per vertex (three 64-bit words and two list slots) plus, for the lists
+ * of long rows, 8 bytes per 4096 entries and 8 (12 when pulling) per GRX_BFSM_BIG_ROW entries. */
+int grx_bfs_multi(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, int32_t n_sources,
+                  int32_t* d_depths, int64_t* h_reached, int64_t* h_depth_sum,
+                  int32_t* h_eccentricity, const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
