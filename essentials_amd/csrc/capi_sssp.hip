@@ -41,6 +41,12 @@ extern "C" int grx_sssp(grx_context_t ctx, grx_graph_t g, int32_t source, float*
       problem.packed_labels = packed && o.sssp_two_pass == 0;
       // the unpacking pass at the end of a packed run also counts what the run reached
       problem.collect_reach = stats != nullptr && problem.packed_labels;
+      // wide pending sets are expanded nearest half first (clients.hxx, select_near): where the label
+      // scan exists and the run ends by itself on one GPU; GRX_SSSP_NEAR=0 switches it off
+      problem.near_far = env_flag("GRX_SSSP_NEAR", true) && problem.packed_labels &&
+                         lb == operators::load_balance_t::block_mapped && !o.call_every_edge &&
+                         !o.holes_layout && o.max_iterations == 0 && !ctx->mc->communicator().attached() &&
+                         (unsigned long long)G.get_number_of_edges() < (1ull << 32);
       problem.init();
       problem.reset();
       enactor_properties_t props;
@@ -52,6 +58,8 @@ extern "C" int grx_sssp(grx_context_t ctx, grx_graph_t g, int32_t source, float*
       enactor.bound_filter = env_flag("GRX_SSSP_BOUND_FILTER", o.call_every_edge == 0);
       enactor.early_live = env_flag("GRX_SSSP_EARLY_LIVE", enactor.early_live);
       enactor.bound_from = (int)env_or("GRX_SSSP_BOUND_FROM", enactor.bound_from, INT_MIN, INT_MAX);
+      if (const char* e = std::getenv("GRX_SSSP_NEAR_FRAC"))  // for the sweep behind the default
+        enactor.near_frac = std::min(1.0, std::max(1.0 / 64, std::atof(e)));
       const float ms = enactor.enact();
       if (stats) {
         run_stats(stats, ms, enactor.iteration, ctx->single());

@@ -555,6 +555,14 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
   // labels only fall, so a sink's older bound stays an upper bound; before that the scan leaves
   // bound16[sink] as resize() left it and the bounds do not count as fresh.
   bool bounds_complete = false;
+  // Near / far selection (sssp_enactor_t::select_near): pend[v] != 0 -- v's label fell since v was
+  // last expanded and v has not been handed to an advance since.  Written by the selection passes
+  // alone, never by an advance; only the ids the label scan visits have one.  near_bins: the work
+  // histogram by distance code (zero between selections), near_threshold: the chosen code.
+  bool near_far = false;
+  hip::device_array_t<unsigned char> pend;
+  hip::device_array_t<unsigned long long> near_bins;
+  hip::device_array_t<unsigned> near_threshold;
   // renumbered graph (see bfs_problem_t): distances are delivered as distance[scatter_to[v]], or
   // gathered through the inverse permutation when the owner has it on the device
   const vertex_t* scatter_to = nullptr;
@@ -598,6 +606,12 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
 #endif
     if (packed_labels)
       bound16.resize(n);
+    near_far = near_far && packed_labels;
+    if (near_far) {
+      pend.resize(n);
+      near_bins.resize(hip::kernels::NEAR_BINS);
+      near_threshold.resize(1);
+    }
   }
   /// bound16[v] <- ceil16(ordered bits of the current distance): one pass, on the context's stream.
   void snapshot_bounds() {
@@ -619,6 +633,10 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
     const std::size_t n = (std::size_t)this->get_graph().get_number_of_vertices();
     const vertex_t s = source;
     bounds_fresh = bounds_complete = false;  // bound16 describes the labels of an earlier run, or nothing
+    if (near_far) {
+      pend.zero(ctx->stream());
+      near_bins.zero(ctx->stream());
+    }
     if (packed_labels) {
       unsigned long long* p = packed.data();
       const unsigned long long zero = (unsigned long long)ordered_bits(weight_t(0)) << 32;
@@ -694,6 +712,10 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
   int bound_from = -1;       // >= 0: first iteration that uses it (experiments); -1: by edges expanded so far
   bool early_live = true;    // the batched form before that point too (hot-first graphs), live labels beyond the image
   const bool debug = std::getenv("GRX_DEBUG") != nullptr;  // read once per run: one line per iteration
+  // Near / far selection: a wide pending set is expanded nearest half first.
+  double near_frac = 0.33;                 // share of the pending work one round takes (profiles/sssp_near_ab.txt)
+  unsigned long long deferred_work = 0;    // work of what the last selection left pending
+  bool input_is_near = false;              // select_near() built the input frontier
 
   sssp_enactor_t(problem_type* p, std::shared_ptr<gcuda::multi_context_t> ctx,
                  enactor_properties_t props = enactor_properties_t())
@@ -739,6 +761,115 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
     E->swap_frontier_buffers();
   }
 
+  /// The next frontier of a round of `work` edges that ran without an output frontier: with deferral
+  /// while something is pending or the round was wide enough for its successor to be, else the plain
+  /// scan (a wide successor of a narrow round is split when its turn comes: loop()).
+  void scan_next(const unsigned long long* packed, unsigned this_round, unsigned long long work,
+                 gcuda::multi_context_t& context) {
+    auto ctx = context.get_context(0);
+    if (near_on(*ctx) && (deferred_work != 0 || work >= ctx->options().sssp_near_min_work))
+      select_near(packed, this_round, context);
+    else
+      scan_improved(packed, this_round, context);
+  }
+
+  /// Near / far selection is part of this run (the problem holds its state) and switched on.
+  bool near_on(gcuda::standard_context_t& ctx) {
+    return this->get_problem()->near_far && ctx.options().sssp_near_min_work != 0 &&
+           ctx.options().label_scan_min_work != 0;
+  }
+
+  /// scan_improved() with deferral: the vertices lowered in round `this_round` join the pending set;
+  /// of the pending set, the part whose distance code is at or below an adaptive threshold -- the
+  /// smallest at which it holds the share near_frac of the pending work -- becomes the next
+  /// frontier, the rest stays pending (everything goes when the pending work is small).  Three
+  /// kernels and the one hand-off scan_improved() has; `this_round` = 0xffffffff: nobody was lowered
+  /// (split_input(): the caller has just marked a frontier's entries pending).
+  void select_near(const unsigned long long* packed, unsigned this_round, gcuda::multi_context_t& context) {
+    namespace k = hip::kernels;
+    auto E = this->get_enactor();
+    auto P = this->get_problem();
+    auto G = P->get_graph();
+    auto ctx = context.get_context(0);
+    const std::size_t n_scan = G.properties.leading_connected ? (std::size_t)G.properties.leading_connected
+                                                              : (std::size_t)G.get_number_of_vertices();
+    unsigned short* bound16 = P->bound16.data();
+    unsigned char* pend = P->pend.data();
+    const unsigned* threshold = P->near_threshold.data();
+    // pass 1: the bounds as scan_improved() leaves them, pend |= lowered in this round, and the
+    // pending work by distance code
+    auto visit = [packed, this_round, bound16, pend] __device__(vertex_t const& v) -> int {
+      const unsigned long long label = packed[v];
+      const unsigned bits = (unsigned)(label >> 32);
+      const unsigned up = (bits >> 16) + ((bits & 0xffffu) ? 1u : 0u);
+      const unsigned b = up > 0xffffu ? 0xffffu : up;
+      bound16[v] = (unsigned short)b;
+      bool pending = pend[v] != 0;
+      if (!pending && (unsigned)label == this_round) {
+        pend[v] = 1;
+        pending = true;
+      }
+      return pending ? (int)k::near_code(b) : -1;
+    };
+    const unsigned long long min_total =
+        std::max(ctx->options().sssp_near_min_work, ctx->options().label_scan_min_work);
+    hip::clocked_t clock(*ctx);  // select_range below stops it: one interval for the three kernels
+    operators::filter::choose_near(G, n_scan, visit, P->near_bins.data(), P->near_threshold.data(), min_total,
+                                   near_frac, *ctx);
+    // pass 2: the near part leaves the pending set
+    auto near = [bound16, pend, threshold] __device__(vertex_t const& v) -> bool {
+      if (!pend[v] || k::near_code(bound16[v]) > *threshold)
+        return false;
+      pend[v] = 0;
+      return true;
+    };
+    operators::filter::select_range(G, n_scan, near, *E->get_output_frontier(), *ctx);
+    P->bounds_fresh = n_scan == (std::size_t)G.get_number_of_vertices() || P->bounds_complete;
+    selected_near(context);
+  }
+
+  /// After a selection's hand-off: what stays deferred, the frontiers swapped, the debug line.
+  void selected_near(gcuda::multi_context_t& context) {
+    auto E = this->get_enactor();
+    auto ctx = context.get_context(0);
+    const unsigned long long total = ctx->workspace().mirror()[hip::kernels::C_PENDING];
+    const unsigned long long taken = E->get_output_frontier()->work_hint();
+    deferred_work = total > taken ? total - taken : 0ull;
+    E->swap_frontier_buffers();
+    input_is_near = true;
+    if (debug) {
+      unsigned t = 0;
+      GRX_HIP_CHECK(hipMemcpy(&t, this->get_problem()->near_threshold.data(), sizeof t, hipMemcpyDeviceToHost));
+      std::fprintf(stderr, "[grx] sssp near: iteration %d threshold %u near_work %llu deferred_work %llu\n",
+                   (int)this->iteration, t, taken, deferred_work);
+    }
+  }
+
+  /// Before a wide iteration: the input frontier (an advance's output, or a plain label scan's)
+  /// becomes the pending set and select_near() hands back its near part -- by the same pass over the
+  /// labels, so that the near part is an ascending frontier like every other wide input.  (Measured
+  /// and not kept: the two passes over the frontier's 30 K - 160 K elements instead, with an
+  /// unordered result -- cheaper passes, but two of six RMAT-22 sources ran 0.25 ms slower.)
+  void split_input(const unsigned long long* packed, gcuda::multi_context_t& context) {
+    auto E = this->get_enactor();
+    auto P = this->get_problem();
+    auto G = P->get_graph();
+    auto ctx = context.get_context(0);
+    const std::size_t n_scan = G.properties.leading_connected ? (std::size_t)G.properties.leading_connected
+                                                              : (std::size_t)G.get_number_of_vertices();
+    const vertex_t* in = E->get_input_frontier()->data();
+    unsigned char* pend = P->pend.data();
+    hip::for_each_index(
+        E->get_input_frontier()->get_number_of_elements(),
+        [in, pend, n_scan] __device__(std::size_t i) {
+          const vertex_t v = in[i];
+          if (v >= 0 && (std::size_t)v < n_scan)  // beyond it: no out-edges, nothing to expand
+            pend[v] = 1;
+        },
+        ctx->stream());
+    select_near(packed, 0xffffffffu, context);
+  }
+
   /// GRX_DEBUG: which form this iteration takes.  Packed labels: A plain,
   /// B label scan, C bounded, D bounded + scan, E early-live (`scan`: it ran without an output and the
   /// label scan built the next frontier; `snapshot`: snapshot_bounds() ran first).  T: the reference's
@@ -756,6 +887,20 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
     auto E = this->get_enactor();
     auto P = this->get_problem();
     auto G = P->get_graph();
+    // Near / far selection: a wide frontier that is not yet the near part of a pending set is split
+    // before it is expanded (RMAT-22: the 9 K hubs the source's iteration found, 90 M edges, most of
+    // which would be expanded again one round later with better distances)
+    const bool from_near = input_is_near;
+    input_is_near = false;
+    if (P->packed_labels && !from_near) {
+      auto ctx = context.get_context(0);
+      const unsigned long long work = E->get_input_frontier()->work_hint();
+      if (near_on(*ctx) && deferred_work == 0 && work != frontier_t::unknown_work &&
+          work >= ctx->options().sssp_near_min_work && work >= ctx->options().label_scan_min_work) {
+        split_input(P->packed.data(), context);
+        input_is_near = false;  // says how the NEXT input was built: set again if this iteration scans
+      }
+    }
     P->log.note(E->get_input_frontier()->get_number_of_elements(),
                 E->get_input_frontier()->work_hint());
 
@@ -879,17 +1024,19 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
             const unsigned b = bound;
             return b != 0xffffu && problem_type::ordered_bits(through) >= (b << 16);
           };
-          const bool scan = ctx->options().label_scan_min_work && work >= ctx->options().label_scan_min_work;
+          // while deferred work remains only a label scan can name the next frontier
+          const bool scan = deferred_work != 0 ||
+                            (ctx->options().label_scan_min_work && work >= ctx->options().label_scan_min_work);
           note_form(reached_enough ? (scan ? 'D' : 'C') : 'E', scan, snapshot);
           auto run = [&](auto hinted) {
             if (scan) {
               // no output frontier: the round tag in a label's low word says "lowered in this round"
-              ctx->options().defer_sync_of_none_output = true;  // scan_improved below is its hand-off
+              ctx->options().defer_sync_of_none_output = true;  // the scan below is its hand-off
               operators::advance::execute<lb, operators::advance_direction_t::forward,
                                           operators::advance_io_type_t::vertices,
                                           operators::advance_io_type_t::none>(G, E, hinted, context);
               ctx->options().defer_sync_of_none_output = false;
-              scan_improved(packed, this_round, context);
+              scan_next(packed, this_round, work, context);
             } else {
               operators::advance::execute<lb>(G, E, hinted, context);
             }
@@ -919,14 +1066,14 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
         const unsigned long long work = E->get_input_frontier()->work_hint();
         if (lb == load_balance_t::block_mapped && !ctx->options().holes_layout &&
             ctx->options().label_scan_min_work && work != frontier_t::unknown_work &&
-            work >= ctx->options().label_scan_min_work) {
+            (work >= ctx->options().label_scan_min_work || deferred_work != 0)) {
           note_form('B', true, false);
-          ctx->options().defer_sync_of_none_output = true;  // scan_improved below is its hand-off
+          ctx->options().defer_sync_of_none_output = true;  // the scan below is its hand-off
           operators::advance::execute<lb, operators::advance_direction_t::forward,
                                       operators::advance_io_type_t::vertices,
                                       operators::advance_io_type_t::none>(G, E, relax_packed, context);
           ctx->options().defer_sync_of_none_output = false;
-          scan_improved(packed, this_round, context);
+          scan_next(packed, this_round, work, context);
           return;
         }
       }

@@ -183,6 +183,27 @@ void select_range(graph_t& G, std::size_t n, pred_t pred, frontier_t& output,
   output.set_ascending(true);
 }
 
+/**
+ * @brief The two passes in front of a near / far selection (compact_kernels.hxx, near_far.hxx):
+ * `visit(v)` for every v in [0, n) returns the distance code of a pending v, -1 otherwise; then `*threshold` <- the smallest code at which the pending work reaches
+ * the share `frac` of its total (NEAR_ALL when the total is below `min_total`), and the total to
+ * counter C_PENDING.  `bins`: NEAR_BINS device words, zero on entry and on exit.  Only enqueues: the
+ * select_range that follows on the same stream, with the predicate "pending and code <= *threshold",
+ * is the hand-off.
+ */
+template <typename graph_t, typename visit_t>
+void choose_near(graph_t& G, std::size_t n, visit_t visit, unsigned long long* bins, unsigned* threshold, unsigned long long min_total, double frac,
+                 gcuda::standard_context_t& context) {
+  namespace k = ::gunrock::hip::kernels;
+  using vertex_t = typename graph_t::vertex_type;
+  const unsigned grid = hip::grid_for(n, k::NEAR_BLOCK, (unsigned)context.compute_units() * 2);
+  k::near_scan_kernel<vertex_t><<<grid, k::NEAR_BLOCK, 0, context.stream()>>>(G, n, visit, bins);
+  GRX_HIP_CHECK(hipGetLastError());
+  k::near_choose_kernel<0><<<1, k::NEAR_BLOCK, 0, context.stream()>>>(
+      bins, threshold, context.workspace().counters() + k::C_PENDING, min_total, frac);
+  GRX_HIP_CHECK(hipGetLastError());
+}
+
 /// Frontier-level entry (reference filter.hxx:59-86).
 template <filter_algorithm_t alg_type, typename graph_t, typename operator_t, typename frontier_t>
 void execute(graph_t& G, operator_t op, frontier_t* input, frontier_t* output,

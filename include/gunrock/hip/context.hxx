@@ -213,6 +213,10 @@ struct operator_options_t {
   /// for free); 0 = never.  Below it the advance packs its output as before.  (RMAT-22, mean of 6
   /// sources, BFS + SSSP enact: 3.21 ms from 16 M, 3.15 from 8 M, 3.10-3.15 from 2 M, 1 M and 512 K.)
   unsigned long long label_scan_min_work = 2ull << 20;
+  /// SSSP: a pending set (the frontier a wide iteration is about to expand, plus what earlier rounds
+  /// deferred) of at least this many edges of work is split by distance -- the near part is
+  /// expanded, the far part waits while its labels fall (clients.hxx, near_far.hxx); 0 = never.
+  unsigned long long sssp_near_min_work = 32ull << 20;
   /// An advance WITHOUT an output frontier normally waits for its kernels like every operator.
   /// true (set by a client around ONE such call, when an operator that fetches the counters follows
   /// at once on the same stream -- operators::filter::select_range): it only enqueues; the next
@@ -336,6 +340,8 @@ class standard_context_t {
       options_.settled_min_work = (unsigned long long)std::atoll(e);
     if (const char* e = std::getenv("GRX_LABEL_SCAN_MIN_WORK"))
       options_.label_scan_min_work = (unsigned long long)std::atoll(e);
+    if (const char* e = std::getenv("GRX_SSSP_NEAR_MIN_WORK"))
+      options_.sssp_near_min_work = (unsigned long long)std::atoll(e);
     if (const char* e = std::getenv("GRX_BY_DESTINATION"))
       options_.by_destination_min_edges = (unsigned long long)std::atoll(e);  // 0: never, 1: always
     if (const char* e = std::getenv("GRX_CHUNK_QUEUE_LIMIT"))

@@ -21,6 +21,7 @@
 
 #include <type_traits>
 
+#include <gunrock/hip/kernels/near_far.hxx>
 #include <gunrock/hip/primitives.hxx>
 #include <gunrock/util/type_limits.hxx>
 
@@ -228,6 +229,77 @@ __global__ void __launch_bounds__(SEL_BLOCK)
       t += s_work[w];
     if (t)
       atomicAdd(&counters[work_slot], t);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Near / far selection (near_far.hxx): the two small kernels in front of a select_range whose
+// predicate is "pending and at or below the threshold".
+//
+//   near_scan_kernel    one pass over the ids: `visit(i)` updates the client's pending state (and
+//                       whatever else the client refreshes from the label it reads anyway) and
+//                       returns the distance code of a pending id, -1 otherwise; the degrees of
+//                       the pending ids are summed per code -- per workgroup in LDS (32-bit bins:
+//                       the caller keeps graphs of 2^32 edges and more away), flushed once per
+//                       workgroup to the 64-bit global bins;
+//   near_choose_kernel  one workgroup: prefix sum over the bins, the threshold to a device word
+//                       (where the selection's predicate reads it: no host wait), the total
+//                       pending work to a counter slot the selection's hand-off carries to the
+//                       host, the bins back to zero.
+// ---------------------------------------------------------------------------
+constexpr int NEAR_BLOCK = 1024;
+
+template <typename vertex_t, typename graph_t, typename visit_t>
+__global__ void __launch_bounds__(NEAR_BLOCK)
+    near_scan_kernel(graph_t G, std::size_t n, visit_t visit, unsigned long long* __restrict__ bins) {
+  __shared__ unsigned s_bins[NEAR_BINS];
+  for (int b = threadIdx.x; b < NEAR_BINS; b += NEAR_BLOCK)
+    s_bins[b] = 0u;
+  __syncthreads();
+  for (std::size_t i = blockIdx.x * (std::size_t)NEAR_BLOCK + threadIdx.x; i < n;
+       i += (std::size_t)gridDim.x * NEAR_BLOCK) {
+    const vertex_t v = (vertex_t)i;
+    const int code = visit(v);
+    if (code >= 0 && code < NEAR_BINS) {
+      const unsigned degree = (unsigned)G.get_number_of_neighbors(v);
+      if (degree)
+        atomicAdd(&s_bins[code], degree);
+    }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < NEAR_BINS; b += NEAR_BLOCK) {
+    const unsigned c = s_bins[b];
+    if (c)
+      atomicAdd(&bins[b], (unsigned long long)c);
+  }
+}
+
+template <int unused = 0>  // a template so that every translation unit may define it
+__global__ void __launch_bounds__(NEAR_BLOCK)
+    near_choose_kernel(unsigned long long* bins, unsigned* threshold, unsigned long long* pending_work,
+                       unsigned long long min_total, double frac) {
+  __shared__ unsigned long long s_waves[NEAR_BLOCK / wave_size + 1];
+  constexpr int PER = NEAR_BINS / NEAR_BLOCK;  // 4 consecutive bins per thread
+  unsigned long long local[PER], sum = 0;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    // read and clear: the bins were filled by device-scope atomics
+    local[k] = __hip_atomic_exchange(&bins[threadIdx.x * PER + k], 0ull, __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_AGENT);
+    sum += local[k];
+  }
+  unsigned long long total = 0;
+  const unsigned long long before = block_exclusive_sum<NEAR_BLOCK>(sum, total, s_waves);
+  const bool all = total == 0 || total < min_total;
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(pending_work, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (all)
+      *threshold = NEAR_ALL;
+  }
+  if (!all) {
+    const int at = near_find(local, PER, before, near_target(total, frac));
+    if (at >= 0)  // exactly one thread: the cumulative work crosses the target once
+      *threshold = (unsigned)(threadIdx.x * PER + at);
   }
 }
 
