@@ -221,6 +221,8 @@ _SIGNATURES = {
     "grx_truss": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_bfs_multi": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, C.POINTER(_Options),
                                 C.POINTER(_Stats)]),
+    "grx_ppr": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_float, C.c_float, _VP, _VP, _VP, C.POINTER(_Options),
+                          C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -893,6 +895,56 @@ def bfs_multi(ctx: Context, g: Graph, sources=None, depths=None, want_depths: bo
            "grx_bfs_multi")
     summary = {"reached": reached[:count], "depth_sum": depth_sum[:count], "eccentricity": eccentricity[:count]}
     return depths, summary, Stats._from(s)
+
+
+def ppr(ctx: Context, g: Graph, seeds=None, alpha: float = 0.85, tol: float = 1e-6, p=None,
+        options: Optional[Options] = None):
+    """Batched personalized PageRank, 64 seeds to a wavefront -> (float32 ranks [count, V] on the
+    device, info, Stats).
+
+    `seeds`: None (every vertex), one vertex, or a sequence / numpy array of vertices, as for
+    `bfs_multi`; a vertex named twice is a row of its own.  Row i is the PageRank vector restarted at
+    seed i: the power iteration of `pagerank` with the teleport and the dangling mass returned to the
+    seed (networkx.pagerank(personalization={s: 1})), so each row sums to 1.  A row stops after the
+    first iteration whose largest change is below `tol`, or after Options.max_iterations when that is
+    non-zero (tol <= 0 needs it), and is frozen from then on: it is bit-identical to the single-seed
+    call whatever else is in the list, and the same call returns identical values
+    (include/essentials_amd.h).  A directed graph needs its in-edges (`g.build_in_edges(ctx)`); an
+    asymmetric CSR without them raises EngineError.  `p`: float32 contiguous tensor of count * V
+    elements on the context's device, allocated when None.  `info` is a dict of numpy arrays of
+    count: `iterations` (int32) and `residual` (float32, the last largest change).  Options read:
+    collect_kernel_time and max_iterations.  Stats.iterations is the sum over batches of 64 of the
+    batch's largest iteration count, Stats.vertices_reached the entries > 0 and Stats.frontier_slots
+    the unfrozen rows of the first batch per iteration."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if seeds is None:
+        h, n, count = None, 0, g.n_rows
+    else:
+        h = np.ascontiguousarray(np.atleast_1d(np.asarray(seeds)), dtype=np.int32)
+        if h.ndim != 1:
+            raise ValueError("ppr: seeds must be one vertex or a flat list of vertices")
+        n = count = int(h.size)
+        if n == 0:  # an empty list is not "every vertex": hand the ABI a non-NULL pointer
+            h = np.zeros(1, np.int32)
+    if p is None:
+        p = torch.empty((count, g.n_rows), dtype=torch.float32, device=device)
+    else:
+        if not isinstance(p, torch.Tensor) or p.dtype != torch.float32:
+            raise TypeError("ppr: p must be a float32 torch tensor")
+        if p.numel() != count * g.n_rows or not p.is_contiguous():
+            raise ValueError(f"ppr: p must be a contiguous tensor of {count} x {g.n_rows} elements")
+        if p.device != device:
+            raise ValueError(f"ppr: p must live on {device}")
+        p = p.view(count, g.n_rows)
+    iterations = np.zeros(max(count, 1), np.int32)
+    residual = np.zeros(max(count, 1), np.float32)
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_ppr(ctx._h, g._h, _ptr(h), n, alpha, tol, _ptr(p) if p.numel() else None,
+                                  _ptr(iterations), _ptr(residual), C.byref(o), C.byref(s)), "grx_ppr")
+    return p, {"iterations": iterations[:count], "residual": residual[:count]}, Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

@@ -598,6 +598,72 @@ int grx_truss(grx_context_t ctx, grx_graph_t g, int32_t* d_truss, int32_t* h_max
 int grx_bfs_multi(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, int32_t n_sources,
                   int32_t* d_depths, int64_t* h_reached, int64_t* h_depth_sum,
                   int32_t* h_eccentricity, const grx_options* opt, grx_stats* stats);
+/* Batched personalized PageRank: one rank vector per seed, 64 seeds to a wavefront.  No reference
+ * counterpart: the reference's ppr.hxx is an approximate forward push with float atomics; this is the
+ * power iteration of grx_pagerank restarted at one vertex, with every sum in a fixed order.
+ * h_seeds: HOST int32[n_seeds] in the caller's numbering; NULL = every vertex 0..V-1 (n_seeds must
+ * then be 0): the convention of grx_bc and grx_bfs_multi.  Let count be the number of seeds.  A
+ * repeated seed is a column of its own.  A non-NULL list with n_seeds == 0, and V == 0, are GRX_OK:
+ * nothing is written, nothing is launched, stats (when given) is zeroed.
+ * Weights are read as they are, as grx_sssp and grx_pagerank read them.  W(u) is the float32 sum of
+ * row u's weights, computed once per call by a fixed tree (lane l of a wavefront adds entries l,
+ * l + 64, ... in order; the 64 sums meet in a butterfly).  u is DANGLING when W(u) == 0: an empty
+ * row, or weights that sum to 0.  scale[u] = alpha / W(u), or 0 when dangling: grx_pagerank's
+ * quantities.
+ * Iteration, for seed s: p_0 = e_s and
+ *   p_{t+1}[v] = sum over in-entries (u -> v, w) of (p_t[u] * scale[u]) * w
+ *                + [v == s] * ((1 - alpha) + alpha * D_t),   D_t = sum of p_t[u] over dangling u.
+ * Dangling mass returns to the seed (networkx.pagerank(personalization={s: 1})); each column sums to
+ * 1; the mean over all V seeds is the grx_pagerank vector; alpha means what it means there.
+ * Stop: column i stops after the first iteration t >= 1 with max_v |p_t[v] - p_{t-1}[v]| < tol
+ * (grx_pagerank's test), and after opt->max_iterations iterations when that is non-zero.  The column
+ * is FROZEN from then on: it does not change while other columns of its batch go on, so a column's
+ * values do not depend on which other seeds are in the list or how they fall into batches.
+ * tol <= 0 means "never by tol"; max_iterations must then be > 0.  A column that is never below tol
+ * (NaN weights) ends the call with GRX_ERR_RUNTIME after 2^20 iterations.
+ * d_p: device float[count * V] out, overwritten, required.  Row i is at [i * V, (i + 1) * V), an
+ * index computed in 64 bits.  h_iterations (HOST int32[count], may be NULL): the iterations column i
+ * ran.  h_residual (HOST float[count], may be NULL): its last max-difference.
+ * Reproducibility: no float atomics.  Every sum is taken in an order fixed by the in-entry layout, V
+ * and one constant, GRX_PPR_SEGMENT: the number of entries of an in-row that one lane group sums
+ * (default 512, minimum 64; an environment variable read per call, a test hook).  An in-row of at
+ * most that many entries is summed sequentially in row order from 0, one fused multiply-add per
+ * entry; a longer one is cut into segments of that size, each summed so, and the partial sums are
+ * added in segment order.  D_t is a two-stage tree over the ascending list of dangling vertices:
+ * chunks of 1024 summed in list order, the chunk sums added in chunk order.  The order never depends
+ * on the grid size, the CU count or arrival order: the same call returns bit-identical values, row i
+ * of a batched call is bit-identical to the single-seed call, changing the hook may change last
+ * bits, and whenever every term and every partial sum is representable in float32 the result is the
+ * exact value.
+ * Which edges: with in-edges attached (grx_graph_build_in_edges) the sum runs over those arrays and
+ * their values.  Without them the handle's own rows serve as in-rows when the CSR is symmetric (an
+ * unknown verdict is verified first, as for pull PageRank); an asymmetric CSR without in-edges is
+ * GRX_ERR_UNSUPPORTED and the message names grx_graph_build_in_edges.
+ * Errors, all found on the host before anything is launched: GRX_ERR_INVALID_ARGUMENT for a NULL ctx
+ * or g, a NULL d_p with count * V > 0, n_seeds < 0, h_seeds == NULL with n_seeds != 0, a seed out of
+ * range, n_rows != n_cols, alpha not in [0, 1) or NaN, a NaN tol, tol <= 0 with max_iterations == 0
+ * and max_iterations < 0.
+ * opt may be NULL; collect_kernel_time and max_iterations are read, everything else is ignored.
+ * Method: the seeds are taken 64 at a time in list order.  State is vertex-major, p[V][L] and two
+ * arrays give[V][L] = p * scale that take turns, L the smallest of 16, 32 and 64 that holds the
+ * batch; lane = column, so an in-entry costs one load of (source, weight) and one contiguous
+ * L * 4-byte read of give[source].  A single seed therefore idles 15 lanes of 16.  One host
+ * hand-off per iteration; the rows are delivered by a transpose through LDS.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (the kernels, batch of
+ * launches by batch, when collect_kernel_time is set), advance_launches (kernel launches),
+ * iterations (the sum over batches of the batch's largest h_iterations: defined by the answer),
+ * edges_traversed = edges_expanded = nnz * that sum, vertices_reached (the (seed, vertex) pairs with
+ * d_p > 0, counted from the delivered values), levels_recorded (min(iterations of the FIRST batch,
+ * 64)) and frontier_slots[t] (the columns of the first batch not yet frozen when its iteration
+ * t + 1 begins; frontier_slots[0] is the batch's width).
+ * The call builds and uses no hot-first copy, leaves nothing on the handle but a symmetry verdict
+ * ensure_can_pull may have produced, and releases its workspace when it returns: per vertex 12 L
+ * bytes of state (768 at L = 64), 4 of scale, 4 of the dangling list and 2 of flags; plus, per
+ * GRX_PPR_SEGMENT entries of the graph, 24 bytes of lists and per segment of a long in-row 4 L bytes of partial
+ * sums; plus 4 L bytes per 1024 dangling vertices. */
+int grx_ppr(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds, int32_t n_seeds, float alpha,
+            float tol, float* d_p, int32_t* h_iterations, float* h_residual, const grx_options* opt,
+            grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
