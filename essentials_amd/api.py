@@ -215,6 +215,10 @@ _SIGNATURES = {
     "grx_color": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_cc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_scc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_lpa": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(_Options),
+                          C.POINTER(_Stats)]),
+    "grx_modularity": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                 C.POINTER(C.c_uint64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_mst": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP,
                           C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_spgemm": (C.c_int, [_VP, _VP, _VP, C.POINTER(_VP), C.POINTER(_Options), C.POINTER(_Stats)]),
@@ -761,6 +765,52 @@ def scc(ctx: Context, g: Graph, components=None, options: Optional[Options] = No
     _check(load_library().grx_scc(ctx._h, g._h, _ptr(components), C.byref(count), C.byref(o), C.byref(s)),
            "grx_scc")
     return components, int(count.value), Stats._from(s)
+
+
+def lpa(ctx: Context, g: Graph, communities=None, options: Optional[Options] = None):
+    """Communities of a symmetric CSR by semi-synchronous label propagation over the colour classes
+    of `color` -> (int32 labels on the device, number of communities as an int, modularity as a
+    float, Stats).
+
+    labels[v] is the smallest vertex id of the community that holds v, the convention of `cc`.  A
+    sweep lets every vertex of one colour class at a time take the most frequent label among its
+    neighbours (repeats count, self loops do not; it keeps its own when that is among the most
+    frequent, else the one of smallest fmix32: include/essentials_amd.h), and the call stops after
+    the first sweep that changes nothing or after Options.max_iterations sweeps: a function of the
+    CSR alone, the same on every call.  `communities`: int32 contiguous tensor of V on the context's
+    device, allocated when None and filled in place otherwise.  The modularity is `modularity` of the
+    result.  Stats.iterations is the number of sweeps, Stats.frontier_slots the labels changed per
+    sweep and Stats.vertices_reached V - communities."""
+    communities = _vertex_output(ctx, g, communities, "lpa", "communities")
+    count = C.c_int64()
+    q = C.c_double()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_lpa(ctx._h, g._h, _ptr(communities), C.byref(count), C.byref(q), C.byref(o),
+                                  C.byref(s)), "grx_lpa")
+    return communities, int(count.value), float(q.value), Stats._from(s)
+
+
+def modularity(ctx: Context, g: Graph, labels):
+    """Modularity of a labelling in exact integers -> (Q as a float, I = the entries whose ends share
+    a label, S = the sum over labels of (the row lengths of its vertices) squared), with E = nnz and
+    Q = I / E - S / E^2 (0.0 when E == 0).
+
+    `labels`: int32 contiguous tensor of V on the context's device with values in [0, V), such as
+    the result of `lpa`, `cc` or `scc`; a value outside raises EngineError.  Every entry counts as
+    given, self loops and repeats included; on a simple symmetric graph this is
+    networkx.community.modularity at resolution 1."""
+    if labels is None:
+        raise TypeError("modularity: labels must be an int32 torch tensor")
+    labels = _vertex_output(ctx, g, labels, "modularity", "labels")
+    q = C.c_double()
+    inside = C.c_int64()
+    squares = C.c_uint64()
+    ctx.after_torch()
+    _check(load_library().grx_modularity(ctx._h, g._h, _ptr(labels), C.byref(q), C.byref(inside), C.byref(squares),
+                                         None, None), "grx_modularity")
+    return float(q.value), int(inside.value), int(squares.value)
 
 
 def mst(ctx: Context, g: Graph, entries=None, components=None, options: Optional[Options] = None):

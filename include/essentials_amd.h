@@ -412,6 +412,84 @@ int grx_cc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_co
  * handle but the symmetry verdict and releases its workspace when it returns. */
 int grx_scc(grx_context_t ctx, grx_graph_t g, int32_t* d_component, int64_t* h_components,
             const grx_options* opt, grx_stats* stats);
+/* Community detection (no reference counterpart: the reference has no such algorithm).
+ * SEMI-SYNCHRONOUS LABEL PROPAGATION (Cordasco, Gargano 2010; the method behind
+ * networkx.community.label_propagation_communities) over the colour classes of grx_color: a
+ * function of the CSR arrays alone, and the same call returns bit-identical values.  The float
+ * values are ignored (as grx_bc ignores them), a repeated entry counts each time it appears, a self
+ * loop is ignored and the order of a row's entries does not matter.  color[] is exactly what
+ * grx_color returns for the handle.  Start: label[v] = v.  A SWEEP takes the colour classes in order
+ * c = 0, 1, ..., num_colors - 1; every vertex v of a class decides at once, from the labels as they
+ * stand when its class begins: count(l) is the number of entries (v, u) of row v with u != v and
+ * label[u] == l, and best the largest count.  v keeps its label when its row has no entry other than
+ * self loops, or when count(label[v]) == best; otherwise it takes, among the labels with count ==
+ * best, the one of smallest fmix32(l) (grx_color's hash: a bijection, so there is no tie left).
+ * Vertices of one class are never adjacent, so deciding at once equals deciding one by one in any
+ * order.  The call stops after the first sweep that changes no label, or after opt->max_iterations
+ * sweeps when that is not 0.  A vertex that moves from a to b has count(b) > count(a), which on a
+ * symmetric CSR raises the number of entries whose ends share a label by 2 * (count(b) - count(a));
+ * that number is at most nnz, so at most nnz / 2 sweeps change anything, and running more than
+ * nnz / 2 + 2 sweeps is GRX_ERR_RUNTIME (it cannot happen unless the kernels are wrong).
+ * d_community: device int32[V] out, overwritten; d_community[v] is the SMALLEST VERTEX ID that ends
+ * with the same label as v: the convention of grx_cc, so d_community[v] <= v and v names its
+ * community iff d_community[v] == v.  h_communities: HOST out, the number of distinct final labels
+ * (an isolated vertex is a community of its own).  h_modularity: HOST out, what grx_modularity
+ * returns for d_community.  At least one of the three must be non-NULL (GRX_ERR_INVALID_ARGUMENT
+ * otherwise); with d_community == NULL the call works on an array of its own.  NULL ctx or g,
+ * n_rows != n_cols and max_iterations < 0 are GRX_ERR_INVALID_ARGUMENT; a handle with in-edges
+ * attached, or a CSR that is not its own transpose (verified once when unknown), is
+ * GRX_ERR_UNSUPPORTED.  V == 0 is GRX_OK with *h_communities = 0, *h_modularity = 0.0 and nothing
+ * written.  opt may be NULL; only collect_kernel_time and max_iterations are read.
+ * Method: the vertices are sorted once by (colour, row-length bin).  A decision gathers label[u]
+ * per entry into a table of (label, count) in LDS -- open addressing, compare-and-swap on the key,
+ * integer add on the count, at most half full: 8 lanes and 64 slots per row up to 32 entries, a
+ * wavefront and 512 slots up to 256, a workgroup of 256 threads and two slots per entry up to
+ * GRX_LPA_BIG_ROW entries (default 4096), and above that, as a whole row, a workgroup of 1024
+ * threads with the largest table the device's LDS holds (GRX_LPA_LDS_SLOTS lowers it; for tests).
+ * A row with more distinct labels than half that table -- a hub in the first sweep -- is decided
+ * again by the same workgroup code on a table of two slots per entry in global memory.  A dirty
+ * byte per vertex: a vertex decides only while its byte is set, and a vertex that changes its label
+ * sets the byte of every other vertex in its row; a vertex none of whose neighbours changed would
+ * decide the same, so labels and sweeps are those of the definition (GRX_LPA_ALL_ROWS = 1 decides
+ * every vertex every sweep; for tests).  A sweep is one launch per non-empty bin of every class,
+ * except that consecutive classes of at most 1024 vertices and GRX_LPA_NARROW_EDGES entries (default
+ * 16384; 0 = never) run inside one workgroup; one hand-off per sweep carries its change count.
+ * stats may be NULL; set: elapsed_ms (the whole call, the colouring included), advance_kernel_ms
+ * (the call's own kernels, batch by batch, when collect_kernel_time is set; the colouring's are not
+ * in it), advance_launches (the call's own kernel launches), iterations (the sweeps run, counting
+ * the last one, which changed nothing), levels_recorded = min(iterations, 64), frontier_slots[t]
+ * (the labels that changed in sweep t + 1; never microseconds, with or without
+ * collect_kernel_time), vertices_reached (V - communities), edges_traversed = nnz, edges_expanded
+ * (the row entries of the deciding vertices plus those of the vertices that changed, whose rows are
+ * walked again to set the dirty bytes; iterations * nnz under GRX_LPA_ALL_ROWS; re-reads inside one
+ * decision do not count).  The colouring's own stats are not reported.  The call builds and uses no
+ * hot-first copy, leaves no state on the handle but the symmetry verdict and releases its workspace
+ * when it returns: 13 bytes per vertex (colours 4, sort keys 4, class lists 4, dirty bytes 1), 4
+ * more each when d_community is NULL and when h_modularity is asked for, the sort's temporary
+ * storage while it runs, and 16 bytes per entry of the rows above GRX_LPA_BIG_ROW of the one class
+ * that has most of them. */
+int grx_lpa(grx_context_t ctx, grx_graph_t g, int32_t* d_community, int64_t* h_communities,
+            double* h_modularity, const grx_options* opt, grx_stats* stats);
+/* Modularity of any labelling, in exact integers.  d_label: device int32[V] with values in [0, V)
+ * (the outputs of grx_lpa, grx_cc and grx_scc qualify); a label outside that range is found by a
+ * device pass before anything is reported and is GRX_ERR_INVALID_ARGUMENT.  E = nnz: every entry
+ * counts as given, self loops and repeats included, and the float values are ignored.  I is the
+ * number of entries whose two ends carry the same label, tot(l) the sum of the row lengths of the
+ * vertices labelled l and S the sum over l of tot(l)^2 (S <= E^2 < 2^62).  Then
+ *     *h_modularity = (double)I / (double)E - (double)S / ((double)E * (double)E)
+ * computed on the host in exactly this form, 0.0 when E == 0.  h_inside_entries receives I and
+ * h_degree_squares S; each of the three may be NULL, at least one must not be.  On a simple
+ * symmetric graph without self loops this is networkx.community.modularity at resolution 1.  A
+ * directed CSR is accepted (no in-edges are needed, attached ones are ignored), but the value is
+ * then NOT the standard directed modularity, which multiplies out-degree by in-degree sums.
+ * n_rows != n_cols is GRX_ERR_INVALID_ARGUMENT.  Only integer atomics and integer reductions are
+ * used, so results are bit-identical from call to call.  opt may be NULL; only collect_kernel_time
+ * is read.  stats may be NULL; set: elapsed_ms, advance_kernel_ms, advance_launches, iterations = 1,
+ * edges_traversed = edges_expanded = nnz.  Workspace: 4 bytes per vertex and 8 bytes per 2048
+ * entries (the segments of long rows), released on return. */
+int grx_modularity(grx_context_t ctx, grx_graph_t g, const int32_t* d_label, double* h_modularity,
+                   int64_t* h_inside_entries, uint64_t* h_degree_squares, const grx_options* opt,
+                   grx_stats* stats);
 /* Minimum spanning FOREST of the CSR as given (the reference's mst.hxx returns one float total,
  * accumulated by float atomics, on connected graphs only, and no edges; this is not a port of it).
  * Every row entry e = (u, v, w) is an undirected candidate edge, whatever its direction; e is the
