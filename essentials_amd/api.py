@@ -227,6 +227,8 @@ _SIGNATURES = {
                                 C.POINTER(_Stats)]),
     "grx_ppr": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_float, C.c_float, _VP, _VP, _VP, C.POINTER(_Options),
                           C.POINTER(_Stats)]),
+    "grx_random_walk": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_float, C.c_float,
+                                  _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -995,6 +997,59 @@ def ppr(ctx: Context, g: Graph, seeds=None, alpha: float = 0.85, tol: float = 1e
     _check(load_library().grx_ppr(ctx._h, g._h, _ptr(h), n, alpha, tol, _ptr(p) if p.numel() else None,
                                   _ptr(iterations), _ptr(residual), C.byref(o), C.byref(s)), "grx_ppr")
     return p, {"iterations": iterations[:count], "residual": residual[:count]}, Stats._from(s)
+
+
+def random_walk(ctx: Context, g: Graph, starts=None, length: int = 80, seed: int = 0, weighted: bool = False,
+                p: float = 1.0, q: float = 1.0, walks_per_start: int = 1, walks=None,
+                options: Optional[Options] = None):
+    """Random walks, one lane per walk -> (int32 walks [count, length + 1] on the device, Stats).
+
+    `starts`: None (every vertex), one vertex, or a sequence / numpy array of vertices, as `ppr` reads
+    its seeds; a vertex named twice is two walks with different draws, and `walks_per_start` > 1
+    repeats every start that many times, consecutively.  Row i is start_i, v_1, ..., v_length; a walk
+    that meets a dead end (an empty row; when `weighted`, a row whose weights do not sum above 0)
+    stops there and the rest of its row is -1.  `weighted`: entries are taken in proportion to their
+    weights instead of uniformly.  `p`, `q` in [0.125, 8]: node2vec's return and in-out parameters, by
+    rejection; with both 1 the walk is first-order.  Every draw is a function of (`seed`, i, step), so
+    the same call returns the same tensor, and row i does not depend on what else is in the list
+    (include/essentials_amd.h has the definition).  A directed graph is walked along its out-entries.
+    `walks`: int32 contiguous tensor of count * (length + 1) elements on the context's device,
+    allocated when None.  Options read: collect_kernel_time.  Stats.iterations is the longest walk's
+    steps, Stats.vertices_reached the walks of full length, Stats.edges_traversed the steps taken,
+    Stats.edges_expanded the candidates drawn and Stats.frontier_slots[t - 1] the walks that took
+    step t."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if walks_per_start < 1:
+        raise ValueError("random_walk: walks_per_start must be at least 1")
+    if starts is None and walks_per_start == 1:
+        h, n, count = None, 0, g.n_rows
+    else:
+        h = np.arange(g.n_rows) if starts is None else np.atleast_1d(np.asarray(starts))
+        if h.ndim != 1:
+            raise ValueError("random_walk: starts must be one vertex or a flat list of vertices")
+        h = np.ascontiguousarray(np.repeat(h, walks_per_start), dtype=np.int32)
+        n = count = int(h.size)
+        if n == 0:  # an empty list is not "every vertex": hand the ABI a non-NULL pointer
+            h = np.zeros(1, np.int32)
+    width = int(length) + 1
+    if walks is None:
+        walks = torch.empty((count, max(width, 0)), dtype=torch.int32, device=device)
+    else:
+        if not isinstance(walks, torch.Tensor) or walks.dtype != torch.int32:
+            raise TypeError("random_walk: walks must be an int32 torch tensor")
+        if length < 0 or walks.numel() != count * width or not walks.is_contiguous():
+            raise ValueError(f"random_walk: walks must be a contiguous tensor of {count} x {width} elements")
+        if walks.device != device:
+            raise ValueError(f"random_walk: walks must live on {device}")
+        walks = walks.view(count, width)
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_random_walk(ctx._h, g._h, _ptr(h), n, length, seed, int(bool(weighted)), p, q,
+                                          _ptr(walks) if walks.numel() else None, C.byref(o), C.byref(s)),
+           "grx_random_walk")
+    return walks, Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

@@ -742,6 +742,66 @@ int grx_bfs_multi(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, in
 int grx_ppr(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds, int32_t n_seeds, float alpha,
             float tol, float* d_p, int32_t* h_iterations, float* h_residual, const grx_options* opt,
             grx_stats* stats);
+/* Random walks: first-order uniform and weighted walks and node2vec (second-order, by rejection),
+ * the corpus of DeepWalk / node2vec and of random-walk samplers.  No reference counterpart.  Every
+ * draw comes from a counter-based generator, so the answer is a function of the CSR and the arguments
+ * alone: walk i is the same bits in every call, and depends neither on the schedule, nor on how walks
+ * are grouped into launches, nor on which other walks are in the list.
+ * h_starts: HOST int32[n_starts]; NULL = every vertex 0..V-1 (n_starts must then be 0): the convention
+ * of grx_bc, grx_bfs_multi and grx_ppr.  Let count be the number of walks; a vertex named twice is two
+ * walks with different draws.  A non-NULL list with n_starts == 0, and V == 0, are GRX_OK: nothing is
+ * written, nothing is launched, stats (when given) is zeroed.
+ * d_walks: device int32[count * (length + 1)] out, row-major, indexed in 64 bits, required.  Row i is
+ * start_i, v_1, ..., v_length; a walk that meets a DEAD END stops there and its remaining slots are
+ * -1.  A dead end is an empty row and, when `weighted`, a row whose total W (below) is not > 0.
+ * length == 0 writes the starts only.  A directed CSR is walked along its out-entries; attached
+ * in-edges are ignored.  A repeated entry counts each time it appears; a self loop is a step like
+ * any other.
+ * Draws, with mix64 the splitmix64 finaliser of x + 0x9E3779B97F4A7C15 (grx_graph_rmat's):
+ *   r(i, t, j) = mix64(mix64(seed ^ mix64(i)) + ((uint64)t << 32) + j)   mod 2^64,
+ * i the 64-bit index of the walk in the list, t = 1..length the step, j the draw inside the step, and
+ * u24(r) = (float)(r >> 40) * 2^-24, exact and in [0, 1).
+ * Candidate of row v (d entries, in row order) from a draw r:
+ *   weighted == 0: entry k = ((r >> 32) * d) >> 32 in 64-bit integers.  Entries are not exactly
+ *     equally likely: the bias is at most d / 2^32 per entry.
+ *   weighted != 0: probability proportional to the entry's float value, through a prefix array c whose
+ *     order is part of the definition.  The row is cut into blocks of 64 entries in row order; inside
+ *     block b, l_k is the sequential float32 sum of the block's weights up to k; the block bases are
+ *     B_0 = 0, B_{b+1} = fl(B_b + l_last(b)); c_k = fl(B_b + l_k), non-decreasing for non-negative
+ *     weights; W = c_{d-1}; x = fl(u24(r) * W).  The candidate is the smallest k with c_k > x and, when
+ *     there is none (the product rounded up to W), the smallest k with c_k == W.  An entry of weight 0
+ *     is never chosen.  With negative or NaN weights the result is unspecified, but the search never
+ *     leaves the row.
+ * Step t of walk i at v, having come from prev (none at t == 1): attempts a = 0, 1, ...; the candidate
+ * x of attempt a comes from r(i, t, 2a); it is accepted at once when t == 1 or ratio == 1, otherwise
+ * iff u24(r(i, t, 2a + 1)) < ratio, where ratio is `ret` if x == prev, `adj` if the entry prev -> x
+ * exists (whatever the order of row prev) and `far` otherwise.  The three are computed once, in
+ * float32: ip = 1/p, iq = 1/q, m = max(ip, 1, iq), ret = ip / m, adj = 1 / m, far = iq / m: node2vec
+ * by rejection.  With p == q == 1 every ratio is 1 and the walk is the first-order walk, bit for bit.
+ * After GRX_WALK_MAX_ATTEMPTS rejected attempts the last candidate is taken (default and maximum
+ * 1024, minimum 1; an environment variable read per call, a test hook).  The cap makes the loop
+ * finite and is a bias: with p, q in [0.125, 8] the smallest ratio is 1/64, so a step reaches the cap
+ * with probability below (63/64)^1024, about 1e-7, and then takes a candidate it might have rejected.
+ * Errors, all found on the host before anything is launched: GRX_ERR_INVALID_ARGUMENT for a NULL ctx
+ * or g, n_starts < 0, h_starts == NULL with n_starts != 0, a start out of range, length < 0,
+ * n_rows != n_cols, p or q NaN or outside [0.125, 8], a NULL d_walks with count > 0 and V > 0, and
+ * opt->max_iterations != 0.  opt may be NULL; only collect_kernel_time is read.
+ * Method: one lane per walk, one launch.  A weighted call first builds c (4 bytes per entry, plus 4
+ * per block of 64 and 4 per vertex while it is built) and selects by binary search in it; a call with
+ * p != 1 or q != 1 and length > 1 first builds a copy of the columns with every row sorted (4 bytes
+ * per entry; 16 more and the sort's workspace while it is built), in which it looks prev -> x up.
+ * Both are built per call; no hot-first copy is built or used, nothing is left on the handle, and the
+ * workspace is released on return.
+ * stats may be NULL; set: elapsed_ms (the whole call), advance_kernel_ms (its kernels, when
+ * collect_kernel_time is set), advance_launches (this library's kernels: the walker, 3 more for c, 2
+ * more for the sorted rows), iterations (the largest number of steps any walk took),
+ * vertices_reached (walks that took all `length` steps), edges_traversed (steps taken: the
+ * non-negative entries of d_walks minus count), edges_expanded (candidates drawn; equal to
+ * edges_traversed when p == q == 1), levels_recorded (min(iterations, 64)) and frontier_slots[t - 1]
+ * (walks that took step t). */
+int grx_random_walk(grx_context_t ctx, grx_graph_t g, const int32_t* h_starts, int32_t n_starts,
+                    int32_t length, uint64_t seed, int32_t weighted, float p, float q,
+                    int32_t* d_walks, const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)
