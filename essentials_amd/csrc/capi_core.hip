@@ -97,8 +97,12 @@ grx_graph_s* essentials_amd::hot_copy(grx_context_s* ctx, grx_graph_s* g, bool c
   std::lock_guard<std::mutex> lock(g->hot_mutex);
   if (g->in_edges && !csr_only)
     return nullptr;  // attached after the copy was made: the copy has no transpose
+  // The copy carries no transpose.  Its view may pass its CSR off as its own in-rows only when that
+  // is KNOWN to be true: a caller that attached in-edges says the graph is directed, and nobody
+  // has compared the CSR with its transpose then (ensure_can_pull returns before it would).
+  const int copy_symmetry = g->in_edges ? (int)grx_graph_s::asymmetric : g->symmetry;
   if (g->hot) {
-    g->hot->symmetry = g->symmetry;  // may have been verified since
+    g->hot->symmetry = copy_symmetry;  // may have been verified, or in-edges attached, since
     return g->hot_first == 0 ? nullptr : g->hot.get();
   }
   int want = g->hot_first;
@@ -124,7 +128,7 @@ grx_graph_s* essentials_amd::hot_copy(grx_context_s* ctx, grx_graph_s* g, bool c
   h->adopt();
   h->max_degree = g->max_degree;
   h->max_degree_known = true;
-  h->symmetry = g->symmetry;  // renumbering keeps (a)symmetry
+  h->symmetry = copy_symmetry;  // renumbering keeps (a)symmetry
   h->hot_first = 0;           // a copy has no copy of its own
   {  // descending degree order: the vertices with edges come first -- how many are there?
     const int32_t* hap = h->d_ap;

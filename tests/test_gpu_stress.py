@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+import pr_oracle
+
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
 
 INF_I = 2**31 - 1
@@ -165,10 +167,22 @@ def test_random_pagerank_pull_and_push(env, oracle):
         if not sym:
             g.build_in_edges(ctx)
         want, it = oracle.pagerank(Ap, Aj, Ax, 0.85, 1e-6)
+        ten = pr_oracle.reference(Ap, Aj, Ax, 0.85, 10)
+        indeg = pr_oracle.in_degrees(Ap, Aj)
         for pull in (True, False):
             p, st = ea.pagerank(ctx, g, 0.85, 1e-6, options=ea.Options(direction_optimized=pull))
             p = host(p)
             assert np.abs(p - want).max() < 5e-6 and abs(st.iterations - it) <= 1, (trial, pull, scale, sym)
+            # exactly 10 iterations (tol = 0 is never met), every vertex within the rounding bound of
+            # the float64 restatement (tests/pr_oracle.py)
+            p, st = ea.pagerank(ctx, g, 0.85, 0.0, options=ea.Options(direction_optimized=pull,
+                                                                      max_iterations=10))
+            p64, allowed = ten
+            r = pr_oracle.ratio(host(p), p64, allowed)
+            v = int(np.argmax(r))
+            assert st.iterations == 10 and (np.abs(host(p).astype(np.float64) - p64) <= allowed).all(), (
+                trial, pull, scale, sym, f"vertex {v} (in-degree {int(indeg[v])}): {r[v]:.3f} x allowed")
+            print(f"\n[pagerank] stress trial {trial} pull={pull}: largest |got - p| / allowed = {r[v]:.3f}")
         g.close()
 
 
