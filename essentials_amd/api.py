@@ -229,6 +229,8 @@ _SIGNATURES = {
                           C.POINTER(_Stats)]),
     "grx_random_walk": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_float, C.c_float,
                                   _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_neighbor_sample": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_uint64, _VP, C.c_int64, _VP, _VP,
+                                      _VP, C.c_int64, _VP, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_advance": (C.c_int, [_VP, _VP, C.POINTER(_Options), C.c_int32, _VP, C.c_int32, _VP,
                               C.c_int64, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "grx_filter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP,
@@ -1050,6 +1052,75 @@ def random_walk(ctx: Context, g: Graph, starts=None, length: int = 80, seed: int
                                           _ptr(walks) if walks.numel() else None, C.byref(o), C.byref(s)),
            "grx_random_walk")
     return walks, Stats._from(s)
+
+
+@dataclass
+class NeighborSample:
+    """What `neighbor_sample` returns: int32 device tensors `nodes` (vertex ids in the graph's numbering,
+    in local-id order), `src`, `dst` (local ids) and `entries` (positions in the column array), and the
+    Python lists `node_offsets` (level L is nodes[node_offsets[L]:node_offsets[L + 1]]) and
+    `edge_offsets` (hop h is [edge_offsets[h - 1], edge_offsets[h]))."""
+    nodes: object
+    src: object
+    dst: object
+    entries: object
+    node_offsets: list
+    edge_offsets: list
+
+
+def neighbor_sample(ctx: Context, g: Graph, seeds=None, fanouts=(25, 10), seed: int = 0,
+                    options: Optional[Options] = None):
+    """Multi-hop fan-out neighbour sampling without replacement -> (NeighborSample, Stats).
+
+    `seeds`: None (every vertex), one vertex, or a sequence / numpy array of vertices; repeats are
+    dropped.  `fanouts`: per hop, at most that many entries of each expanded row (1..1024), or -1 for
+    every entry.  Hop h expands the vertices first reached in hop h - 1; a vertex is expanded once.
+    `nodes[src]`, `nodes[dst]` is the global edge list, and `torch.stack([dst, src])` is a PyG
+    `edge_index` (messages flow from the sampled neighbour to the expanded vertex) into `x[nodes]`;
+    `entries` indexes the graph's column and value arrays.  Every draw is a function of (`seed`, vertex,
+    hop), so the same call returns the same tensors and a vertex's sample does not depend on the other
+    seeds: vary `seed` per batch (include/essentials_amd.h has the definition).  A directed graph is
+    sampled along its out-entries.  The tensors are allocated by the bounds that never fail and
+    returned as slices of the true lengths.  Options read: collect_kernel_time.  Stats.iterations is
+    the hops that expanded a vertex, Stats.vertices_reached the nodes, Stats.edges_traversed the sampled
+    edges, Stats.edges_expanded the candidates drawn (a row taken whole counts its length) and
+    Stats.frontier_slots[h - 1] the vertices expanded in hop h."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    fan = np.ascontiguousarray(np.atleast_1d(np.asarray(fanouts)), dtype=np.int32)
+    if fan.ndim != 1:
+        raise ValueError("neighbor_sample: fanouts must be one fan-out or a flat list of them")
+    hops = int(fan.size)
+    if seeds is None:
+        h, n, distinct = None, 0, g.n_rows
+    else:
+        h = np.atleast_1d(np.asarray(seeds))
+        if h.ndim != 1:
+            raise ValueError("neighbor_sample: seeds must be one vertex or a flat list of vertices")
+        h = np.ascontiguousarray(h, dtype=np.int32)
+        n, distinct = int(h.size), int(np.unique(h).size)
+        if n == 0:  # an empty list is not "every vertex": hand the ABI a non-NULL pointer
+            h = np.zeros(1, np.int32)
+    # the bounds that never fail
+    nnz, edge_cap, level = int(g.nnz), 0, distinct
+    for k in fan.tolist():
+        e = nnz if k < 1 else min(level * k, nnz)  # a bad fan-out is the ABI's to refuse
+        edge_cap, level = edge_cap + e, min(e, g.n_rows)
+    edge_cap = min(edge_cap, nnz)
+    node_cap = min(distinct + edge_cap, g.n_rows)
+    nodes = torch.empty(max(node_cap, 1), dtype=torch.int32, device=device)
+    src, dst, entries = (torch.empty(max(edge_cap, 1), dtype=torch.int32, device=device) for _ in range(3))
+    node_off = np.zeros(hops + 2, np.int64)
+    edge_off = np.zeros(hops + 1, np.int64)
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_neighbor_sample(ctx._h, g._h, _ptr(h), n, _ptr(fan) if hops else None, hops, seed, _ptr(nodes), node_cap,
+                                              _ptr(src), _ptr(dst), _ptr(entries), edge_cap, _ptr(node_off),
+                                              _ptr(edge_off), C.byref(o), C.byref(s)), "grx_neighbor_sample")
+    nn, ne = int(node_off[-1]), int(edge_off[-1])
+    return NeighborSample(nodes[:nn], src[:ne], dst[:ne], entries[:ne], node_off.tolist(), edge_off.tolist()), \
+        Stats._from(s)
 
 
 def advance(ctx: Context, g: Graph, frontier, op: EdgeOp = EdgeOp.all, state=None, iparam: int = 0,

@@ -802,6 +802,91 @@ int grx_ppr(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds, int32_t n_
 int grx_random_walk(grx_context_t ctx, grx_graph_t g, const int32_t* h_starts, int32_t n_starts,
                     int32_t length, uint64_t seed, int32_t weighted, float p, float q,
                     int32_t* d_walks, const grx_options* opt, grx_stats* stats);
+/* Neighbour sampling: multi-hop fan-out sampling WITHOUT replacement, the mini-batch sampler of
+ * GraphSAGE-style training (PyG's NeighborLoader, DGL's sample_neighbors, cuGraph's
+ * uniform_neighbor_sample).  No reference counterpart.  Every draw comes from grx_random_walk's
+ * counter-based generator, so the answer is a function of the CSR and the arguments alone: the same
+ * bits in every call, whatever the schedule and the lane-group widths.
+ * Seeds.  h_seeds: HOST int32[n_seeds]; NULL = every vertex 0..V-1 (n_seeds must then be 0): the
+ * convention of grx_bc, grx_bfs_multi, grx_ppr and grx_random_walk.  Repeats are dropped and the first
+ * occurrence is kept: level 0 of the node list is the distinct seeds in list order.  A non-NULL list
+ * with n_seeds == 0, and V == 0, are GRX_OK: nothing is launched, device outputs are untouched,
+ * offsets (when given) are all 0, stats (when given) is zeroed.
+ * Fan-outs.  h_fanouts: HOST int32[n_hops], 1 <= n_hops <= 64.  k_h in [1, 1024]: at most k_h entries
+ * of each expanded row; k_h == -1: every entry; k_h == 0, k_h < -1 and k_h > 1024 are errors.
+ * Levels.  Node level 0 is the seeds.  Hop h = 1..n_hops expands exactly the vertices of level h - 1,
+ * in node-list order: a vertex is expanded at most once per call, in the hop after it was first
+ * reached (PyG's convention).  Level h is the set of vertices named by hop h's sampled entries that
+ * are in no earlier level, in ascending vertex id.  A vertex's LOCAL id is its index in the node
+ * list.  When a level is empty every later hop samples nothing.
+ * Sample of row v in hop h.  Let d be the row's length, its positions ap[v] .. ap[v] + d - 1 as given,
+ * and k = k_h.
+ *   All: k == -1 or d <= k.  Every entry is taken; no draws are made.
+ *   Otherwise the candidates are x_a = walk_pick_uniform(r(v, h, a), d) = ((r >> 32) * d) >> 32 for
+ *   a = 0, 1, ..., with r(v, h, a) = walk_draw(walk_stream(seed, v), h, a): r(i, t, j) of
+ *   grx_random_walk with i = the vertex id, t = the hop (1-based) and j = the attempt.  Let m = k when
+ *   2k <= d (INCLUDE), else m = d - k (EXCLUDE), so m <= d / 2 always.  S is the first m distinct
+ *   values of the sequence, and A the number of candidates drawn until S is complete: the smallest A
+ *   for which x_0 .. x_{A-1} hold m distinct values.  Include takes the positions in S; exclude takes
+ *   every position of the row not in S.  The chosen entries are emitted in ascending position.
+ *   Every k-subset of the row is equally likely, up to walk_pick_uniform's bias of d / 2^32 per
+ *   entry.  The draws are keyed by the vertex, not by its place in the frontier: the sample of row v
+ *   in hop h under `seed` is the same whichever other seeds are in the list.  A caller varies `seed`
+ *   per batch.
+ *   The loop is bounded at 64 m + 1024 attempts; reaching the bound sets a device flag and the call
+ *   returns GRX_ERR_RUNTIME.  This cannot happen unless the kernels are wrong: while fewer than
+ *   m <= d / 2 positions are held, an attempt names a new one with probability at least
+ *   1/2 - d / 2^33 > 1/4, so the new positions among n = 64 m + 1024 attempts dominate a binomial
+ *   (n, 1/4) count X, and by Hoeffding P(X < m) <= exp(-2 (n/4 - m)^2 / n) with
+ *   n/4 - m = 15 m + 256 > 15 (m + 16) and n = 64 (m + 16): below exp(-7 (m + 16)) <= e^-119 < 2^-171
+ *   per row.
+ * Graph conventions.  A repeated entry is an entry of its own: a sample may hold both copies.  A self
+ * loop is an entry like any other (dst == src, no new vertex).  An empty row contributes nothing.  A
+ * directed CSR is sampled along its out-entries; attached in-edges and a hot-first copy are ignored
+ * and none is built: a host that wants in-neighbours passes the transposed graph.  Float values are
+ * ignored.
+ * Outputs.  Each may be NULL, but not all six; with device outputs NULL the call works on arrays of
+ * its own, so a count-only call is possible.
+ *   d_nodes: device int32[node_capacity]: vertex ids in the caller's numbering, in local-id order.
+ *   h_node_offsets: HOST int64[n_hops + 2]: level L is [off[L], off[L + 1]).
+ *   d_src, d_dst: device int32[edge_capacity]: the LOCAL ids of the expanded vertex and of the
+ *     sampled neighbour.
+ *   d_entry: device int32[edge_capacity]: the entry's position in the column array, the edge id from
+ *     which a caller fetches weights or edge features.
+ *   Edges are ordered hop by hop, then by the expanded vertex's local id, then by ascending position.
+ *   h_edge_offsets: HOST int64[n_hops + 1]: hop h is [off[h - 1], off[h]).
+ * Capacities.  A hop's exact edge count and new-vertex count are known before anything of that hop
+ * is written to caller memory (count pass + scan; claim + count).  If a count does not fit, the call
+ * returns GRX_ERR_RUNTIME and the message names the hop and the number needed; earlier hops' outputs
+ * stay as written.  Bounds that never fail: E_h <= min(|level h - 1| * k_h, nnz), <= nnz for
+ * k_h == -1; the sum of E_h over all hops <= nnz (a row is expanded once); nodes <= min(distinct
+ * seeds + edges, V).
+ * Errors, all found on the host before anything is launched: GRX_ERR_INVALID_ARGUMENT for a NULL ctx,
+ * g or h_fanouts, n_seeds < 0, h_seeds == NULL with n_seeds != 0, a seed out of range, n_hops outside
+ * [1, 64], a bad fan-out, n_rows != n_cols, a negative capacity, all six outputs NULL, and
+ * opt->max_iterations != 0.  opt may be NULL; only collect_kernel_time is read.
+ * Method, per hop: a count pass over the frontier (min(d, k) per row, and the row's lane-group class)
+ * and a scan; the sampler, one group of 8 lanes, a wavefront or a workgroup per row (all-rows by d,
+ * picking rows by m; GRX_SAMPLE_GROUP = 8, 64 or 256 forces one width, 0 = by the rule: an
+ * environment variable read per call, a test hook; neither the answer nor the stats defined below
+ * depend on it): a group draws a group-width of candidates at once into an LDS open-addressing table
+ * of >= 2m slots and decides first occurrences and A in attempt order; discovery (claim
+ * local[u] == -1 by compare-and-swap, sort the claimed ids, assign local ids); and the fill of the
+ * caller's arrays.  Two host hand-offs per hop.
+ * stats may be NULL; set, and defined by the answer: iterations (hops that expanded at least one
+ * vertex), vertices_reached (nodes), edges_traversed (sampled edges), edges_expanded (the sum over
+ * expanded rows of A, counting d for an all-row), levels_recorded (n_hops), frontier_slots[h - 1]
+ * (vertices expanded in hop h); and, defined by the schedule, elapsed_ms, advance_kernel_ms (when
+ * collect_kernel_time is set) and advance_launches (this library's kernels).
+ * The workspace is released on return and nothing is left on the handle: 4 bytes per vertex for the
+ * local-id map (set to -1 per call) and 4 per vertex of the current level; per hop 13 bytes per
+ * frontier row (count, offset, order, two class bytes), 12 per sampled edge of the hop and 8 per
+ * vertex the hop can still discover (min(E_h, V - nodes)), plus rocPRIM's scan and sort storage. */
+int grx_neighbor_sample(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds, int32_t n_seeds,
+                        const int32_t* h_fanouts, int32_t n_hops, uint64_t seed, int32_t* d_nodes,
+                        int64_t node_capacity, int32_t* d_src, int32_t* d_dst, int32_t* d_entry,
+                        int64_t edge_capacity, int64_t* h_node_offsets, int64_t* h_edge_offsets,
+                        const grx_options* opt, grx_stats* stats);
 
 /* ---- operators (frontier-level overloads) -------------------------------- */
 /* operators::advance::execute<lb, forward, in, out>(G, op, input, output, segments, context)

@@ -102,7 +102,9 @@ GRX_WALK_HD inline int walk_ratio_class(int32_t x, int32_t prev, const int32_t* 
   return lo < len && prev_row[lo] == x ? WALK_ADJ : WALK_FAR;
 }
 
-#if defined(__HIPCC__)
+// A translation unit that wants the definition alone (the draws, for another sampler) says so: the
+// kernels below are not templates, and one library holds them once.
+#if defined(__HIPCC__) && !defined(GRX_WALK_DEFINITION_ONLY)
 
 constexpr int WALK_BLOCK = 256;
 constexpr int WALK_PREFIX_THREADS = 128;  // two wavefronts, a 64 x 65 float tile each
