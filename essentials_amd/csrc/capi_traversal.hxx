@@ -61,8 +61,12 @@ bfs_run_t run_bfs_client(problem_t& problem, int64_t n_rows, const grx_options& 
     clients::bfs_enactor_t<problem_t, lb> enactor(&problem, ctx->mc, props);
     enactor.max_iterations = o.max_iterations;
     enactor.mark_without_claim = env_flag("GRX_BFS_MARK", enactor.mark_without_claim);
+    // wide levels of a graph KNOWN to be symmetric pull (no symmetry check is run for this)
+    enactor.pull_wide_levels = env_flag("GRX_BFS_PULL", enactor.pull_wide_levels);
+    if (o.do_alpha > 0) enactor.alpha = o.do_alpha;
     run.ms = enactor.enact();
     run.iterations = enactor.iteration;
+    run.pulls = enactor.pull_iterations;
   }
   return run;
 }

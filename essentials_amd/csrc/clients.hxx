@@ -204,12 +204,29 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
 
   void finalize(gcuda::multi_context_t&) override { this->get_problem()->deliver(); }
 
+  /// Does a label-scan level with `work` frontier edges pull?  Beamer's test on a graph known to be
+  /// its own transpose: more frontier edges than 1 / alpha of the edges not yet expanded (the level
+  /// log has this level's already).  No way back is needed: a level under label_scan_min_work
+  /// leaves the branch that asks.
+  bool pulls(unsigned long long work) {
+    auto G = this->get_problem()->get_graph();
+    if (!pull_wide_levels || max_iterations || !G.properties.symmetric || G.properties.directed ||
+        G.has_in_edges())
+      return false;
+    const unsigned long long nnz = (unsigned long long)G.get_number_of_edges();
+    const unsigned long long logged = (unsigned long long)this->get_problem()->log.edges_expanded;
+    const unsigned long long unexplored = logged < nnz ? nnz - logged : 0;
+    return (double)work > (double)unexplored / alpha;
+  }
+
   /// One level.  `visit` discovers, `has_depth` is its pure "already discovered" test,
   /// `found_now(v)` says that THIS level discovered v (asked after the level), `mark` is visit for a
   /// level whose output nobody reads: it labels an unlabelled destination and returns nothing of use.
-  template <typename visit_t, typename has_depth_t, typename found_t, typename mark_t>
-  void expand(visit_t visit, has_depth_t has_depth, found_t found_now, mark_t mark,
-              gcuda::multi_context_t& context) {
+  /// A pulled level asks `in_level(u)`, "u's depth is the input frontier's", and labels with `adopt(v)`.
+  template <typename visit_t, typename has_depth_t, typename found_t, typename mark_t, typename in_level_t,
+            typename adopt_t>
+  void expand(visit_t visit, has_depth_t has_depth, found_t found_now, mark_t mark, in_level_t in_level,
+              adopt_t adopt, gcuda::multi_context_t& context) {
     auto E = this->get_enactor();
     auto G = this->get_problem()->get_graph();
     // wide levels (block_mapped's fused form): every vertex that has a depth is settled -- visit()
@@ -220,9 +237,13 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
     if (lb == load_balance_t::block_mapped && ctx->options().settled_filter &&
         !ctx->options().holes_layout && work != frontier_t::unknown_work &&
         work >= ctx->options().settled_min_work) {
+      operators::advance::settled_snapshot_t<vertex_t> level_start;
       {  // part of this level's advance: timed with it when kernels are timed
         hip::clocked_t clock(*ctx);
-        settled.refresh((std::size_t)G.get_number_of_vertices(), has_depth, *ctx);
+        // bits a label-scan level left for a LATER level than the one behind it (narrow levels ran in
+        // between) are rebuilt: has_depth as it stands now, for every id the bitmap covers
+        level_start = settled.refresh((std::size_t)G.get_number_of_vertices(), has_depth, *ctx,
+                                      (long long)this->iteration);
         clock.stop();
       }
       if (ctx->options().label_scan_min_work && work >= ctx->options().label_scan_min_work) {
@@ -241,8 +262,20 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
         // the store (calling a store-only functor for the edges the predicate has just passed, without
         // the conditional's load, was measured too: 343 us -- not kept).
         const bool idempotent = ctx->options().settled_filter && mark_without_claim;
+        const std::size_t n_scan = G.properties.leading_connected
+                                       ? (std::size_t)G.properties.leading_connected
+                                       : (std::size_t)G.get_number_of_vertices();
         ctx->options().defer_sync_of_none_output = true;  // select_range below is its hand-off
-        if (idempotent)
+        if (pulls(work)) {
+          // ... and where most of the frontier's edges lead to vertices that have a depth, the
+          // vertices that have none look for ONE frontier neighbour each instead (DESIGN.md section
+          // 5): the level finds the same set, so everything behind it is unchanged.  Who is in the
+          // frontier is asked of the settled bits as they stood when the level began (refresh() above:
+          // an exact snapshot, not the hint a push level takes) and, beyond them, of "its depth is this
+          // level's" -- never of "it has a depth" read live, which this level's own stores change.
+          ++pull_iterations;
+          operators::advance::pull::enqueue_range(G, n_scan, level_start, has_depth, in_level, adopt, *ctx);
+        } else if (idempotent)
           operators::advance::execute<lb, operators::advance_direction_t::forward,
                                       operators::advance_io_type_t::vertices,
                                       operators::advance_io_type_t::none>(
@@ -253,15 +286,13 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
                                       operators::advance_io_type_t::none>(
               G, E, operators::advance::with_settled(visit, settled.view(), has_depth), context);
         ctx->options().defer_sync_of_none_output = false;
-        const std::size_t n_scan = G.properties.leading_connected
-                                       ? (std::size_t)G.properties.leading_connected
-                                       : (std::size_t)G.get_number_of_vertices();
         // the same pass leaves the NEXT level's settled bitmap (what rebuild() would compute then:
         // has_depth as it stands after this level) when the graph is larger than the image
         std::size_t bit_limit = 0;
         unsigned long long* bit_words = nullptr;
         if ((std::size_t)G.get_number_of_vertices() >= operators::advance::settled_max_ids)
-          bit_words = settled.prepare((std::size_t)G.get_number_of_vertices(), bit_limit);
+          bit_words = settled.prepare((std::size_t)G.get_number_of_vertices(), bit_limit,
+                                      (long long)this->iteration + 1);
         operators::filter::select_range</*narrow_claims=*/true>(
             G, n_scan, found_now, *E->get_output_frontier(), *ctx, hip::kernels::select_no_each_t(), has_depth,
             bit_words, bit_limit);
@@ -313,7 +344,12 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
           bytes[(unsigned)dst] = (unsigned char)level;  // a 1-byte store: no neighbour's byte is touched
         return false;
       };
-      expand(visit_byte, has_byte, found_byte, mark_byte, context);
+      const unsigned this_level = (unsigned)this->iteration;
+      auto in_level_byte = [bytes, this_level] __device__(vertex_t const& u) -> bool {
+        return bytes[(unsigned)u] == this_level;
+      };
+      auto adopt_byte = [bytes, level] __device__(vertex_t const& v) { bytes[(unsigned)v] = (unsigned char)level; };
+      expand(visit_byte, has_byte, found_byte, mark_byte, in_level_byte, adopt_byte, context);
       return;
     }
     auto visit = [depth, next_level] __host__ __device__(vertex_t const& src, vertex_t const& dst,
@@ -336,10 +372,16 @@ struct bfs_enactor_t : gunrock::enactor_t<problem_type> {
         depth[dst] = next_level;
       return false;
     };
-    expand(visit, has_depth, found_now, mark, context);
+    const vertex_t this_level = this->iteration;
+    auto in_level = [depth, this_level] __device__(vertex_t const& u) -> bool { return depth[u] == this_level; };
+    auto adopt = [depth, next_level] __device__(vertex_t const& v) { depth[v] = next_level; };
+    expand(visit, has_depth, found_now, mark, in_level, adopt, context);
   }
   operators::advance::settled_filter_t<vertex_t> settled;
   bool mark_without_claim = true;  // label-scan levels label with a plain store (GRX_BFS_MARK=0: the claim)
+  bool pull_wide_levels = true;    // label-scan levels of a symmetric graph may pull (GRX_BFS_PULL=0: never)
+  float alpha = 16.0f;             // Beamer's alpha (bfs_do_enactor_t's is 4; swept on RMAT-20 / 22 / 24)
+  int pull_iterations = 0;
 };
 
 // ---------------------------------------------------------------------------

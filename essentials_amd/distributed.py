@@ -169,10 +169,22 @@ class SingleRunner:
                                 "frac_of_gather_roof": kernel_gteps / max(gather.values()),
                                 "note": "measured live: acc += table[column[i]] over all edges of this "
                                         "graph (4-B entries, |V| of them), no frontier logic, atomics "
-                                        "or output -- the ceiling of any label-testing advance"},
+                                        "or output -- the ceiling of any label-testing PUSH advance: one "
+                                        "lookup per frontier edge.  The widest levels of a symmetric graph "
+                                        "are pulled (an unlabelled vertex stops at its first frontier "
+                                        "neighbour), so the traversal as a whole tests fewer labels than "
+                                        "edges_traversed and this fraction may exceed 1"},
                 "kernel": "BFS advance, all levels of one traversal: settled-bitmap rebuild + "
-                          "classify_hubs_kernel + expand_settled_kernel on the wide levels, "
-                          "block_mapped_kernel + chunk_kernel on the others",
+                          "pull_range_kernel on the pulled wide levels (symmetric graphs), "
+                          "classify_hubs_kernel + expand_settled_kernel on the other wide levels, "
+                          "select_range_kernel behind both, block_mapped_kernel + chunk_kernel on the rest",
+                "measured_fields_note":
+                    "traffic, measured_frac and measured_frac_of_copy_rate are added from the committed counter "
+                    "passes (profiles/latest_pmc.json): the bytes of the search THOSE passes ran, divided by this "
+                    "run's kernel_ms.  Where traffic_detail.traffic_stale is true they say nothing about this "
+                    "traversal: counters collected on the push-only search (1.96 GB per traversal) set against "
+                    "the kernel time of a search that pulls its wide levels and no longer moves those bytes read "
+                    "as near-peak HBM use that does not exist -- meaningless until the passes are re-collected",
                 "call_every_edge_formulation": {
                     "kernel_ms": every.advance_kernel_ms, "enact_ms": every.elapsed_ms,
                     "frac": nbytes / (every.advance_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,

@@ -107,7 +107,11 @@ typedef struct grx_options {
                                    scatter of pr.hxx (one float atomic per edge); 1 the pull form (sums
                                    per destination over in-edges, no atomics).  Pulling needs in-edges:
                                    an undirected graph or grx_graph_build_in_edges                  */
-  float do_alpha;               /* 0: default 4: pull when frontier edges > unexplored edges/alpha   */
+  float do_alpha;               /* 0: default 4: pull when frontier edges > unexplored edges/alpha.
+                                   grx_bfs with direction_optimized == 0 applies the same test
+                                   (0: default 16) to its widest levels on a graph KNOWN to be
+                                   symmetric (R-MAT symmetrised, a symmetric Matrix Market file, or
+                                   verified by an earlier pull call); GRX_BFS_PULL=0 never pulls    */
   float do_beta;                /* 0: default 24: push again when frontier vertices < |V| / beta     */
   int32_t chunk_queue_limit;    /* test hook, 0: none. Caps the hub chunk queue to force the overflow
                                    path (hubs expanded in place)                                    */

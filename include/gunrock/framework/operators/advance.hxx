@@ -763,6 +763,43 @@ void execute(graph_t& G,
   }
 }
 
+/**
+ * @brief A wide level of a search, pulled over the id range [0, n) of a graph that is its OWN
+ * transpose (the caller's knowledge: nothing is checked here) -- no candidate list, no output
+ * frontier (advance_kernels.hxx: pull_range_kernel).  For every v < n that is not `labelled(v)`
+ * the row of v is read from the front; at the first neighbour in the current frontier `label(v)` is
+ * called and the row is left.  A neighbour u is in the frontier when its bit of `snapshot` is set
+ * ("u was labelled when the level began"; u below the snapshot's limit) or, beyond the snapshot, when
+ * `in_level(u)` says so -- the exact "u's label is this level's", which label() never changes.
+ * `snapshot` must be EXACT for every id below its limit (settled.hxx: settled_snapshot_t, what
+ * settled_filter_t::refresh() returns for this level) -- not the one-sided hint an advance takes: a
+ * frontier vertex whose bit is missing is not seen by its neighbours.
+ * One 1024-thread workgroup per CU keeps the snapshot in its LDS (at most settled_max_ids bits).
+ * Only enqueues and leaves the kernel clock running: the operator that names what the level found
+ * (filter::select_range) is its hand-off, as for an advance without an output.
+ */
+template <typename graph_t, typename vertex_t, typename labelled_t, typename in_level_t, typename label_t>
+void enqueue_range(graph_t& G, std::size_t n, settled_snapshot_t<vertex_t> exact_snapshot, labelled_t labelled,
+                   in_level_t in_level, label_t label, gcuda::standard_context_t& context) {
+  namespace k = detail::k;
+  if (n == 0)
+    return;
+  settled_view_t<vertex_t> snapshot = exact_snapshot.exact;
+  if (!snapshot.bits)
+    snapshot.limit = 0;
+  error::throw_if_exception((std::size_t)snapshot.limit > settled_max_ids || snapshot.limit % 128 != 0,
+                            "pull advance: the snapshot does not fit the LDS image");
+  auto kernel = k::pull_range_kernel<graph_t, vertex_t, labelled_t, in_level_t, label_t>;
+  const std::size_t lds = snapshot.limit > 0 ? (std::size_t)snapshot.limit / 8 : 16;
+  static detail::lds_opt_in_t opt_in;  // of this instantiation of the kernel
+  error::throw_if_exception(!opt_in.fits(reinterpret_cast<const void*>(kernel), lds, context),
+                            "pull advance: the snapshot does not fit the LDS image");
+  hip::clocked_t clock(context);
+  kernel<<<hip::grid_for(n, k::SET_BLOCK, (unsigned)context.compute_units()), k::SET_BLOCK, lds,
+           context.stream()>>>(G, n, snapshot, labelled, in_level, label);
+  GRX_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace pull
 
 // ===========================================================================

@@ -13,6 +13,12 @@
  *     return false for THIS edge and change nothing" (SSSP: dist[dst] <= dist[src] + w),
  * and the engine is then free -- not obliged -- to skip the functor call for such an edge.
  *
+ * That is the contract of a HINT (settled_view_t, what with_settled() takes).  A pulled level
+ * (advance.hxx: pull::enqueue_range) reads the same bitmap under a stronger one: as an exact and
+ * complete SNAPSHOT of the predicate at the level's start (settled_snapshot_t, handed out by
+ * settled_filter_t::refresh() only).  Code that weakens the bitmap to what a hint may be -- leaving
+ * old bits in place, covering fewer ids than `limit` -- must not feed a snapshot.
+ *
  * Why.  A wide level is bound by what happens per edge inside the opaque functor: a label lookup
  * (one L2 request per edge) and, where it passes, a memory-side atomic whose round trip every lane
  * of the wavefront waits for; the four calls a lane has in flight are serialised by the compiler
@@ -50,6 +56,16 @@ template <typename vertex_t>
 struct settled_view_t {
   const unsigned* bits = nullptr;  ///< bit v of word v / 32, 16-byte aligned
   vertex_t limit = 0;              ///< ids >= limit are not covered; a multiple of 128
+};
+
+/// The same bitmap under the STRONGER contract a pulled level needs (advance.hxx:
+/// pull::enqueue_range): exact and complete -- bit v is set if and only if the client's predicate held
+/// for v when the level began, for EVERY v below `limit`.  A hint that is stale or partial only costs
+/// an advance some skipped shortcuts; a snapshot that is stale makes a pulled level miss frontier
+/// vertices and label their neighbours late or never.  Only settled_filter_t::refresh() hands one out.
+template <typename vertex_t>
+struct settled_snapshot_t {
+  settled_view_t<vertex_t> exact;
 };
 
 /// The predicate of a client that has a bitmap only.
@@ -185,31 +201,37 @@ class settled_filter_t {
   void clear() { limit_ = 0; }
   /// Another pass is about to write the bitmap (operators::filter::select_range with a bit
   /// predicate): storage for `n_vertices`, returns the word array; `limit` ids are covered.  The
-  /// next rebuild() is then skipped once (the bits are those rebuild() would compute now).
-  unsigned long long* prepare(std::size_t n_vertices, std::size_t& limit) {
+  /// bits it writes are those rebuild() would compute at the start of step `for_step` of the
+  /// caller's loop, and of no other step: refresh(..., for_step) is then skipped, once.
+  unsigned long long* prepare(std::size_t n_vertices, std::size_t& limit, long long for_step) {
     std::size_t ids = n_vertices < settled_max_ids ? n_vertices : settled_max_ids;
     ids = (ids + 127) / 128 * 128;
     if (words_.size() < ids / 64)
       words_.resize(ids / 64);
     limit_ = (vertex_t)ids;
     limit = ids;
-    fresh_ = true;
+    written_for_ = for_step;
     return words_.data();
   }
-  /// rebuild() unless a prepare()d pass has just written the bits.
+  /// rebuild() unless a prepare()d pass wrote the bits for exactly this `step`.  Bits prepared for
+  /// an earlier step that never asked for them (the steps in between ran without a bitmap) are
+  /// OLD: as a hint they would only be weaker, as a snapshot they would be wrong, so they are
+  /// rebuilt.  Returns the bitmap as a SNAPSHOT: for every id below its limit, exactly pred() as it
+  /// stands when the kernels enqueued next on the context's stream begin.
   template <typename pred_t>
-  void refresh(std::size_t n_vertices, pred_t pred, gcuda::standard_context_t& context) {
-    if (fresh_) {
-      fresh_ = false;
-      return;
-    }
-    rebuild(n_vertices, pred, context);
+  settled_snapshot_t<vertex_t> refresh(std::size_t n_vertices, pred_t pred, gcuda::standard_context_t& context,
+                                       long long step) {
+    const bool current = written_for_ == step;
+    written_for_ = -1;
+    if (!current)
+      rebuild(n_vertices, pred, context);
+    return settled_snapshot_t<vertex_t>{view()};
   }
 
  private:
   hip::device_array_t<unsigned long long> words_;
   vertex_t limit_ = 0;
-  bool fresh_ = false;
+  long long written_for_ = -1;  // the step whose opening state a prepare()d pass has written; -1: none
 };
 
 }  // namespace advance

@@ -1691,6 +1691,101 @@ __global__ void __launch_bounds__(ADV_BLOCK)
 }
 
 // ---------------------------------------------------------------------------
+// pull_range_kernel: a wide level of a search on a graph that is its own transpose, pulled over
+// the id range [0, n) with no candidate list and no output: an id the client calls `labelled` is
+// skipped; every other v reads its row from the front and at the first neighbour that is IN THE
+// CURRENT FRONTIER calls label(v) and stops.  Both halves of the pull pair above in one launch: a
+// lane probes at most PULL_PROBES entries of its own row, PULL_GROUP independent column loads in
+// flight; the rows of a wavefront still undecided are then walked by the whole wavefront, 64
+// entries per step, ballot exit -- handed over by shuffles, no queue.
+// "In the current frontier" is decided from what cannot change while the level runs:
+//   - bit u of `snapshot` for u < snapshot.limit: "u was labelled when the level began" (at that
+//     moment every labelled neighbour of an unlabelled vertex is in the frontier), read from the
+//     workgroup's LDS image of the bits -- one 1024-thread workgroup per CU, as
+//     expand_settled_kernel has it (the same bits from global memory at full occupancy, a bitmap of
+//     every id, measured equal at 1 M and 4 M vertices and 7 % slower at 16 M: DESIGN.md section 5);
+//   - in_level(u) beyond: the EXACT test "u's label is this level's" -- label() writes the next
+//     level into unlabelled vertices only, so no store of this launch changes its answer.
+// Never from "u has a label" read live: a vertex labelled a moment ago by this launch would adopt
+// v one level too early.  labelled(v) may be live: only v's owner writes v.
+// ---------------------------------------------------------------------------
+constexpr int PULL_GROUP = 4;
+
+template <typename graph_t, typename vertex_t, typename labelled_t, typename in_level_t, typename label_t>
+__global__ void __launch_bounds__(SET_BLOCK)
+    pull_range_kernel(graph_t G,
+                      std::size_t n,
+                      operators::advance::settled_view_t<vertex_t> snapshot,
+                      labelled_t labelled,
+                      in_level_t in_level,
+                      label_t label) {
+  using edge_t = typename graph_t::edge_type;
+  constexpr int BLOCK = SET_BLOCK;
+  extern __shared__ unsigned s_snapshot[];  // snapshot.limit bits
+  const int lane = lane_id();
+  const vertex_t limit = snapshot.limit;
+  {
+    const unsigned groups = (unsigned)limit / 128u;  // the bitmap is whole 16-byte groups
+    const uint4* src = reinterpret_cast<const uint4*>(snapshot.bits);
+    uint4* dst = reinterpret_cast<uint4*>(s_snapshot);
+    for (unsigned w = threadIdx.x; w < groups; w += BLOCK)
+      dst[w] = src[w];
+  }
+  __syncthreads();
+  auto in_frontier = [&](vertex_t u) -> bool {
+    if ((unsigned)u < (unsigned)limit)
+      return (s_snapshot[(unsigned)u >> 5] >> ((unsigned)u & 31u)) & 1u;
+    return in_level(u);
+  };
+
+  const std::size_t n_tiles = (n + BLOCK - 1) / BLOCK;
+  for (std::size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const std::size_t idx = tile * BLOCK + threadIdx.x;
+    const vertex_t v = (vertex_t)idx;
+    edge_t first = 0;
+    edge_t deg = 0;
+    if (idx < n && !labelled(v)) {
+      first = G.get_starting_edge(v);
+      deg = G.get_starting_edge(v + 1) - first;
+    }
+    bool hit = false;
+    edge_t r = 0;
+    const edge_t stop = deg < (edge_t)PULL_PROBES ? deg : (edge_t)PULL_PROBES;
+    while (r < stop && !hit) {
+      vertex_t u[PULL_GROUP];
+#pragma unroll
+      for (int k = 0; k < PULL_GROUP; ++k)  // past the probe's end: its last entry again
+        u[k] = G.get_destination_vertex(first + (r + k < stop ? r + k : stop - 1));
+#pragma unroll
+      for (int k = 0; k < PULL_GROUP; ++k)
+        hit = in_frontier(u[k]) || hit;
+      r += PULL_GROUP;
+    }
+    if (hit)
+      label(v);
+    // undecided with entries left: one row after the other, the whole wavefront on each
+    unsigned long long more = __ballot(!hit && deg > (edge_t)PULL_PROBES);
+    while (more) {
+      const int owner = __ffsll((long long)more) - 1;
+      more &= more - 1ull;
+      const vertex_t row = __shfl(v, owner, wave_size);
+      const edge_t row_first = __shfl(first, owner, wave_size);
+      const edge_t row_deg = __shfl(deg, owner, wave_size);
+      bool found = false;
+      for (edge_t r0 = (edge_t)PULL_PROBES; r0 < row_deg && !found; r0 += wave_size) {
+        const edge_t at = r0 + lane;
+        bool here = false;
+        if (at < row_deg)
+          here = in_frontier(G.get_destination_vertex(row_first + at));
+        found = __ballot(here) != 0ull;  // wave-uniform
+      }
+      if (found && lane == 0)
+        label(row);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // bucketing: bin valid input slots by degree into three queues.
 //   small  (< BUCKET_SMALL)  -> thread-per-slot        (thread_mapped_kernel)
 //   medium (< hub_threshold) -> wavefront-per-slot     (wave_mapped_kernel)

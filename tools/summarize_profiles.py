@@ -34,7 +34,7 @@ def one(pattern):
 
 ADVANCE = ("block_mapped_kernel", "chunk_kernel", "classify_hubs_kernel", "expand_fused_kernel",
            "expand_settled_kernel", "rebuild_kernel", "pull_probe_kernel",
-           "pull_long_kernel", "select_range_kernel")
+           "pull_long_kernel", "pull_range_kernel", "select_range_kernel")
 
 
 def attribute(name):
@@ -80,7 +80,8 @@ def attribute_all(names):
     for a, b in zip(starts, starts[1:] + [len(out)]):
         run = range(a, b)
         mine = [out[j][0] for j in run if out[j][1] == "bfs"]
-        if "expand_fused_kernel" in mine and "expand_settled_kernel" not in mine:
+        # (a default run whose wide levels were all PULLED has no expand_settled_kernel either)
+        if "expand_fused_kernel" in mine and "expand_settled_kernel" not in mine and "pull_range_kernel" not in mine:
             for j in run:
                 if out[j][1] == "bfs":
                     out[j] = (out[j][0], "bfs_every_edge")
