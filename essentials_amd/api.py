@@ -217,6 +217,8 @@ _SIGNATURES = {
     "grx_scc": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_lpa": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(_Options),
                           C.POINTER(_Stats)]),
+    "grx_louvain": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                              C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_modularity": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                  C.POINTER(C.c_uint64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_mst": (C.c_int, [_VP, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_double), _VP,
@@ -794,6 +796,35 @@ def lpa(ctx: Context, g: Graph, communities=None, options: Optional[Options] = N
     _check(load_library().grx_lpa(ctx._h, g._h, _ptr(communities), C.byref(count), C.byref(q), C.byref(o),
                                   C.byref(s)), "grx_lpa")
     return communities, int(count.value), float(q.value), Stats._from(s)
+
+
+def louvain(ctx: Context, g: Graph, communities=None, options: Optional[Options] = None):
+    """Communities of a symmetric CSR by multi-level modularity optimisation (Louvain) in exact
+    integers -> (int32 labels on the device, number of communities as an int, modularity as a
+    float, levels as an int, Stats).
+
+    labels[v] is the smallest vertex id of the community that holds v, the convention of `cc` and
+    `lpa`.  A phase sweeps the colour classes of `color` on its level graph: every vertex of a class
+    moves to the neighbouring community of largest integer gain k_vc * E - k(v) * tot(c) (smallest
+    fmix32 among equals) when that beats staying; a sweep that does not raise the score is undone
+    and ends the phase, and the communities become the next level's vertices
+    (include/essentials_amd.h states all of it).  A function of the CSR alone, the same bits on
+    every call.  Options.max_iterations, when not 0, is the number of phases: the result is then a
+    cut of the dendrogram.  Resolution is fixed at 1.  `communities`: int32 contiguous tensor of V
+    on the context's device, allocated when None and filled in place otherwise.  The modularity is
+    `modularity` of the result.  `levels` counts the phases run, the last one, which keeps nothing,
+    included.  Stats.iterations is the number of sweeps over all phases, Stats.frontier_slots the
+    moves each kept (0 ends a phase) and Stats.vertices_reached V - communities."""
+    communities = _vertex_output(ctx, g, communities, "louvain", "communities")
+    count = C.c_int64()
+    q = C.c_double()
+    levels = C.c_int32()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_louvain(ctx._h, g._h, _ptr(communities), C.byref(count), C.byref(q), C.byref(levels),
+                                      C.byref(o), C.byref(s)), "grx_louvain")
+    return communities, int(count.value), float(q.value), int(levels.value), Stats._from(s)
 
 
 def modularity(ctx: Context, g: Graph, labels):

@@ -494,6 +494,71 @@ int grx_lpa(grx_context_t ctx, grx_graph_t g, int32_t* d_community, int64_t* h_c
 int grx_modularity(grx_context_t ctx, grx_graph_t g, const int32_t* d_label, double* h_modularity,
                    int64_t* h_inside_entries, uint64_t* h_degree_squares, const grx_options* opt,
                    grx_stats* stats);
+/* Community detection by MULTI-LEVEL MODULARITY OPTIMISATION (Louvain; Blondel et al. 2008), defined
+ * in exact integers: a function of the CSR arrays alone, the same call returns bit-identical values,
+ * and there is no float gain, no float atomic and no random order.  Resolution is fixed at 1; a
+ * resolution parameter, Leiden refinement and directed modularity are out of scope.
+ * Input: as grx_lpa, a square CSR that is its own transpose (verified once when unknown;
+ * GRX_ERR_UNSUPPORTED otherwise, also with in-edges attached).  The float values are ignored.
+ * E = nnz, k(v) is the row length, a repeated entry counts each time: the conventions of
+ * grx_modularity, Q = I / E - S / E^2.
+ * LEVEL GRAPH: n_L vertices, integer weights w(u, v) = w(v, u), k(v) = the sum of row v, the self
+ * entry included.  Level 0 is the handle's CSR with weight 1 per entry, used in place.
+ * PHASE: label[v] = v, tot[c] = k(c).  The vertices are coloured by grx_color on the level graph's
+ * pattern CSR (above level 0: one entry per distinct pair, rows ascending by column, the self
+ * entry present when its weight is positive).  A SWEEP takes the colour classes in order.  Every
+ * vertex v of a class decides from label and tot AS THEY STAND WHEN ITS CLASS BEGINS: for every
+ * label c carried by some entry (v, u) with u != v, k_vc is the sum of those entries' weights;
+ * t(c) = tot[c], minus k(v) when c == label[v]; gain(c) = k_vc * E - k(v) * t(c) as int64 (both
+ * products are below 2^62 because E < 2^31); gain(own) uses k_v,own, which may be 0.  v stays when
+ * it has no entry other than self entries, or when no other label has gain > gain(own); otherwise
+ * it takes the label of largest gain, among equal gains the one of smallest fmix32(c), c being the
+ * level-local id.  When the class is done its moves are applied: label[v], tot[old] -= k(v),
+ * tot[new] += k(v).  Two vertices of one class can interact through tot, so a sweep need not raise
+ * the score: after each sweep N = I * E - S is evaluated in exact integers (I: the weight of the
+ * entries whose two ends share a label, S: the sum of tot^2; both terms below 2^62).  A sweep with
+ * no move ends the phase; a sweep with moves that leaves N <= N_before is UNDONE (label and tot
+ * return to their state before it) and ends the phase.  N rises strictly with every kept sweep,
+ * which bounds the sweeps.  There is no dirty-vertex rule: every vertex with a non-empty row
+ * decides in every sweep.
+ * AGGREGATION: if the phase kept no move the run ends.  Otherwise the communities become the
+ * vertices of the next level, numbered by ascending smallest original vertex id; w'(a, b) is the
+ * sum of w(u, v) over u in a and v in b, the self entry w'(a, a) holding the inside weight.  E and
+ * N are unchanged by construction, and weights stay int32 because every weight is at most E.
+ * STOP: when a phase keeps no move, or after opt->max_iterations phases when that is not 0; the
+ * partition after t phases is then the result (a dendrogram cut).
+ * d_community: device int32[V] out; each entry is the smallest original vertex id in the same final
+ * community (the grx_cc / grx_lpa convention).  h_communities: HOST out.  h_modularity: HOST out,
+ * exactly (double)I / (double)E - (double)S / ((double)E * (double)E) (0.0 when E == 0), bit-equal
+ * to grx_modularity of d_community.  h_levels: HOST out, the phases run, counting the last one,
+ * which keeps nothing.  At least one of the four must be non-NULL; with d_community == NULL the
+ * call works on an array of its own.  NULL ctx or g, n_rows != n_cols and max_iterations < 0 are
+ * GRX_ERR_INVALID_ARGUMENT.  V == 0 is GRX_OK with *h_communities = 0, *h_modularity = 0.0,
+ * *h_levels = 0 and nothing written.  opt may be NULL; only collect_kernel_time and max_iterations
+ * are read.
+ * Method: the schedule and the tables of grx_lpa.  The vertices of a level are sorted once by
+ * (colour, row-length bin); a decision gathers (label[u], w) per entry into a table of (community,
+ * weight sum) in LDS -- 8 lanes and 64 slots per row up to 32 entries, a wavefront and 512 slots
+ * up to 256, a workgroup of 256 threads up to GRX_LOUVAIN_BIG_ROW entries (default 4096), above
+ * that a workgroup of 1024 threads with the largest table the LDS holds (GRX_LOUVAIN_LDS_SLOTS
+ * lowers it; for tests) --, reads tot per occupied slot and reduces to the largest gain, then to
+ * the smallest hash at that gain.  A row with more distinct neighbour communities than half the
+ * table is decided on a table of two slots per entry in global memory.  label[v] is written in
+ * place and tot when the class is done.  Consecutive classes of at most 1024 vertices and
+ * GRX_LOUVAIN_NARROW_EDGES entries (default 16384; 0 = never) run inside one workgroup.  One
+ * hand-off per sweep carries the moves, I and S; a sweep is undone from a copy of label and tot.
+ * Aggregation ranks the communities by a first-occurrence pass and a scan, sorts the 64-bit keys
+ * (rank[label[u]] << 32) | rank[label[v]] with their weights, sums equal keys and reads the next
+ * level's offsets off the sorted keys.
+ * stats may be NULL; set: iterations (the sweeps over all phases, undone and still ones included),
+ * levels_recorded = min(iterations, 64), frontier_slots[t] (the moves KEPT by sweep t: 0 for an
+ * undone or still sweep, so every phase ends in a 0 and the number of zeros is *h_levels),
+ * vertices_reached (V - communities), edges_traversed = nnz, edges_expanded (the sum over sweeps
+ * of that level graph's entry count), advance_launches, elapsed_ms and advance_kernel_ms as in
+ * grx_lpa (aggregation is outside the timed batches).  The colourings' own stats are not reported.
+ * The workspace is released on return and the handle keeps nothing but the symmetry verdict. */
+int grx_louvain(grx_context_t ctx, grx_graph_t g, int32_t* d_community, int64_t* h_communities,
+                double* h_modularity, int32_t* h_levels, const grx_options* opt, grx_stats* stats);
 /* Minimum spanning FOREST of the CSR as given (the reference's mst.hxx returns one float total,
  * accumulated by float atomics, on connected graphs only, and no edges; this is not a port of it).
  * Every row entry e = (u, v, w) is an undirected candidate edge, whatever its direction; e is the

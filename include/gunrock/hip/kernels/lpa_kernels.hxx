@@ -37,6 +37,9 @@
  * other classes and written of this one: nothing is handed between workgroups inside a launch.
  * The one-workgroup kernel does hand labels and flags from class to class; there they are read and
  * written with agent-scope relaxed accesses behind the workgroup's barrier.
+ *
+ * The kernels are `inline`: capi_lpa.hip and capi_louvain.hip (through louvain_kernels.hxx, which
+ * shares the schedule, the table and the first-occurrence pass) both include this header.
  */
 #pragma once
 
@@ -116,10 +119,12 @@ __device__ __forceinline__ unsigned long long lpa_rank(int32_t count, int32_t la
   return ((unsigned long long)(unsigned)count << 32) | (0xffffffffu - fmix32((unsigned)label));
 }
 
-/// Count label l in the table key/cnt[0, cap): `fresh` += 1 when this call took a slot.  False when
-/// `cap` probes found neither l nor an empty slot.  GLOBAL: the table is in global memory.
+/// Count label l in the table key/cnt[0, cap), `w` times (grx_louvain adds an entry's weight):
+/// `fresh` += 1 when this call took a slot.  False when `cap` probes found neither l nor an empty
+/// slot.  GLOBAL: the table is in global memory.
 template <bool GLOBAL>
-__device__ __forceinline__ bool lpa_insert(int32_t* key, int32_t* cnt, unsigned cap, int32_t l, int& fresh) {
+__device__ __forceinline__ bool lpa_insert(int32_t* key, int32_t* cnt, unsigned cap, int32_t l, int& fresh,
+                                           int32_t w = 1) {
   unsigned s = __umulhi((unsigned)l * 0x9e3779b1u, cap);
   for (unsigned probe = 0; probe < cap; ++probe) {
     int32_t seen = GLOBAL ? load_relaxed(&key[s]) : __hip_atomic_load(&key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -131,7 +136,7 @@ __device__ __forceinline__ bool lpa_insert(int32_t* key, int32_t* cnt, unsigned 
       }
     }
     if (seen == l) {
-      atomicAdd(&cnt[s], 1);
+      atomicAdd(&cnt[s], w);
       return true;
     }
     if (++s == cap)
@@ -140,7 +145,7 @@ __device__ __forceinline__ bool lpa_insert(int32_t* key, int32_t* cnt, unsigned 
   return false;
 }
 
-__global__ void __launch_bounds__(LPA_BLOCK) lpa_init_kernel(int32_t* label, unsigned char* dirty, int32_t n) {
+inline __global__ void __launch_bounds__(LPA_BLOCK) lpa_init_kernel(int32_t* label, unsigned char* dirty, int32_t n) {
   for (int64_t v = blockIdx.x * (int64_t)LPA_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * LPA_BLOCK) {
     label[v] = (int32_t)v;
     if (dirty)
@@ -149,7 +154,7 @@ __global__ void __launch_bounds__(LPA_BLOCK) lpa_init_kernel(int32_t* label, uns
 }
 
 /// starts[k] = first position of key k in the sorted keys (k = 0 .. n_keys).
-__global__ void __launch_bounds__(LPA_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BLOCK)
     lpa_starts_kernel(const unsigned* keys, int32_t n, int32_t n_keys, int32_t* starts) {
   for (int64_t k = blockIdx.x * (int64_t)LPA_BLOCK + threadIdx.x; k <= n_keys; k += (int64_t)gridDim.x * LPA_BLOCK) {
     int32_t lo = 0, hi = n;
@@ -166,7 +171,7 @@ __global__ void __launch_bounds__(LPA_BLOCK)
 
 /// entries[k] += the row lengths of the vertices of key k; a wavefront whose 64 positions share a
 /// key adds once.
-__global__ void __launch_bounds__(LPA_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BLOCK)
     lpa_entries_kernel(const unsigned* keys, const int32_t* order, const int32_t* ap, int32_t n,
                        unsigned long long* entries) {
   const int lane = lane_id();
@@ -279,7 +284,7 @@ __device__ __forceinline__ void lpa_group_decide(const lpa_state_t& st, int32_t 
 
 /// The rows rows[0, n_rows) of one class, G lanes each.
 template <int G>
-__global__ void __launch_bounds__(LPA_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BLOCK)
     lpa_group_kernel(lpa_state_t st, const int32_t* rows, int32_t n_rows, lpa_counters_t* ctr) {
   static_assert(G == LPA_SMALL || G == wave_size, "a group is 8 lanes or a wavefront");
   constexpr int SLOTS = G == LPA_SMALL ? LPA_SMALL_SLOTS : LPA_WAVE_SLOTS;
@@ -416,7 +421,7 @@ __host__ __device__ __forceinline__ unsigned lpa_slots_for(int32_t len, int32_t 
  * its flag still set; the pool gives it 4 words per entry.
  */
 template <int BLOCK>
-__global__ void __launch_bounds__(BLOCK)
+inline __global__ void __launch_bounds__(BLOCK)
     lpa_block_kernel(lpa_state_t st, const int32_t* rows, int32_t n_rows, int32_t max_slots, unsigned long long* over,
                      lpa_counters_t* ctr) {
   extern __shared__ int32_t s_dyn[];
@@ -442,7 +447,7 @@ __global__ void __launch_bounds__(BLOCK)
 }
 
 /// The rows on the overflow list, a workgroup each, with a table of two slots per entry in the pool.
-__global__ void __launch_bounds__(LPA_BIG_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BIG_BLOCK)
     lpa_fallback_kernel(lpa_state_t st, const unsigned long long* over, int32_t* pool, lpa_counters_t* ctr) {
   __shared__ lpa_block_lds_t s;
   const int32_t items = ctr->overflow_n;  // written by the kernel before this one; constant here
@@ -466,7 +471,7 @@ __global__ void __launch_bounds__(LPA_BIG_BLOCK)
  * class c.  Dynamic LDS: max(16 wavefront tables, 2 * max_slots) words.  pool: 4 words per entry of
  * the longest row of bins 2 and 3.
  */
-__global__ void __launch_bounds__(LPA_BIG_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BIG_BLOCK)
     lpa_narrow_kernel(lpa_state_t st, const int32_t* order, const int32_t* starts, int32_t c0, int32_t c1,
                       int32_t max_slots, int32_t* pool, lpa_counters_t* ctr) {
   constexpr int WAVES = LPA_BIG_BLOCK / wave_size;
@@ -508,7 +513,7 @@ __global__ void __launch_bounds__(LPA_BIG_BLOCK)
 }
 
 /// The hand-off that ends a sweep: the sweep's changes (cleared for the next) and the entries read.
-__global__ void lpa_publish_kernel(lpa_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
+inline __global__ void lpa_publish_kernel(lpa_counters_t* ctr, unsigned long long* mirror, int sequence_slot,
                                    unsigned long long sequence) {
   if (threadIdx.x == 0) {
     mirror[LPA_CHANGES] = ctr->changes;
@@ -525,7 +530,7 @@ __global__ void lpa_publish_kernel(lpa_counters_t* ctr, unsigned long long* mirr
 /// first[l] = the smallest vertex labelled l (first[] starts as all ones).  A wavefront whose
 /// vertices share a label sends one minimum, and nobody sends what the word already beats: the
 /// final labels of an R-MAT are one giant community, and its word takes ~90 atomics per microsecond.
-__global__ void __launch_bounds__(LPA_BLOCK) lpa_first_kernel(const int32_t* label, int32_t n, unsigned* first) {
+inline __global__ void __launch_bounds__(LPA_BLOCK) lpa_first_kernel(const int32_t* label, int32_t n, unsigned* first) {
   const int lane = lane_id();
   const int64_t stride = (int64_t)gridDim.x * LPA_BLOCK;
   for (int64_t v0 = blockIdx.x * (int64_t)LPA_BLOCK + threadIdx.x - lane; v0 < n; v0 += stride) {
@@ -542,7 +547,7 @@ __global__ void __launch_bounds__(LPA_BLOCK) lpa_first_kernel(const int32_t* lab
 }
 
 /// label[v] = first[label[v]], in place; the vertices that are their own community's name are counted.
-__global__ void __launch_bounds__(LPA_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BLOCK)
     lpa_canonical_kernel(int32_t* label, int32_t n, const unsigned* first, lpa_counters_t* ctr) {
   unsigned long long mine = 0;
   for (int64_t v = blockIdx.x * (int64_t)LPA_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * LPA_BLOCK) {
@@ -556,7 +561,7 @@ __global__ void __launch_bounds__(LPA_BLOCK)
 }
 
 /// bad = 1 when a label is outside [0, n).
-__global__ void __launch_bounds__(LPA_BLOCK) lpa_range_kernel(const int32_t* label, int32_t n, lpa_counters_t* ctr) {
+inline __global__ void __launch_bounds__(LPA_BLOCK) lpa_range_kernel(const int32_t* label, int32_t n, lpa_counters_t* ctr) {
   bool bad = false;
   for (int64_t v = blockIdx.x * (int64_t)LPA_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * LPA_BLOCK) {
     const int32_t l = label[v];
@@ -568,7 +573,7 @@ __global__ void __launch_bounds__(LPA_BLOCK) lpa_range_kernel(const int32_t* lab
 
 /// tot[l] += the row lengths of the vertices labelled l (at most nnz < 2^31 each); the lanes of a
 /// wavefront that share a label add once.
-__global__ void __launch_bounds__(LPA_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BLOCK)
     lpa_tot_kernel(const int32_t* ap, const int32_t* label, int32_t n, unsigned* tot) {
   const int lane = lane_id();
   const int64_t stride = (int64_t)gridDim.x * LPA_BLOCK;
@@ -603,7 +608,7 @@ __global__ void __launch_bounds__(LPA_BLOCK)
 
 /// inside += the entries (v, u) with label[v] == label[u]: chunks of LPA_BLOCK rows flattened over
 /// the workgroup.  Rows above LPA_INSIDE_SEGMENT entries go to the big list in segments ...
-__global__ void __launch_bounds__(LPA_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BLOCK)
     lpa_inside_kernel(const int32_t* ap, const int32_t* aj, const int32_t* label, int32_t n, int2* big,
                       lpa_counters_t* ctr) {
   __shared__ int32_t s_pre[LPA_BLOCK], s_base[LPA_BLOCK], s_wave[LPA_BLOCK / wave_size + 1], s_label[LPA_BLOCK];
@@ -631,7 +636,7 @@ __global__ void __launch_bounds__(LPA_BLOCK)
 }
 
 /// ... which the grid walks a workgroup per segment: no launch is as long as its longest row.
-__global__ void __launch_bounds__(LPA_BLOCK)
+inline __global__ void __launch_bounds__(LPA_BLOCK)
     lpa_inside_big_kernel(const int32_t* ap, const int32_t* aj, const int32_t* label, const int2* big,
                           lpa_counters_t* ctr) {
   const int32_t items = ctr->big_n;  // written by the kernel before this one; constant here
@@ -650,7 +655,7 @@ __global__ void __launch_bounds__(LPA_BLOCK)
 }
 
 /// squares += tot[l]^2 in 64 bits (the sum is at most nnz^2 < 2^62).
-__global__ void __launch_bounds__(LPA_BLOCK) lpa_squares_kernel(const unsigned* tot, int32_t n, lpa_counters_t* ctr) {
+inline __global__ void __launch_bounds__(LPA_BLOCK) lpa_squares_kernel(const unsigned* tot, int32_t n, lpa_counters_t* ctr) {
   unsigned long long sum = 0;
   for (int64_t l = blockIdx.x * (int64_t)LPA_BLOCK + threadIdx.x; l < n; l += (int64_t)gridDim.x * LPA_BLOCK) {
     const unsigned long long t = tot[l];
