@@ -1,12 +1,12 @@
 /** @file capi_louvain.hip  grx_louvain: communities by multi-level modularity optimisation in exact
  * integers (hip/kernels/louvain_kernels.hxx; include/essentials_amd.h states the definition).  No
- * reference counterpart.  A phase colours its level graph with grx_color, sorts the vertices once
- * by (colour, row-length bin) and sweeps: one launch per non-empty bin of every large class and its
- * apply launch, one one-workgroup launch per run of small classes, the score passes, and the one
- * hand-off that carries the sweep's moves, I and S.  The communities of a phase that kept a move
- * are contracted by a radix sort and a reduction by key into the next level graph.  The workspace
- * is released on return; the handle keeps nothing but the symmetry verdict. */
-#include "capi_batch.hxx"
+ * reference counterpart.  A phase builds the schedule of its level graph and sweeps it with the
+ * launches of capi_class_sweep.hxx, shared with grx_lpa; every wide class is followed by its apply
+ * launch, and a sweep ends with the score passes and the one hand-off that carries its moves, I
+ * and S.  The communities of a phase that kept a move are contracted by a radix sort and a
+ * reduction by key into the next level graph.  The workspace is released on return; the handle
+ * keeps nothing but the symmetry verdict. */
+#include "capi_class_sweep.hxx"
 
 #include <gunrock/hip/kernels/louvain_kernels.hxx>
 
@@ -29,13 +29,6 @@ struct level_t {
   hip::device_array_t<int32_t> k;  // k(v); level 0: filled by the phase's init
 };
 
-/// Test hooks and what the device allows.
-struct limits_t {
-  int32_t big_row;
-  unsigned long long narrow_edges;
-  int32_t slots;
-};
-
 /// What a call accumulates over its phases.
 struct tally_t {
   int32_t launches = 0;
@@ -45,12 +38,6 @@ struct tally_t {
   bool scored = false;
 };
 
-/// Consecutive colour classes that one launch sequence serves: one wide class, or a run of small ones.
-struct step_t {
-  int32_t c0, c1;
-  bool narrow;
-};
-
 long long score_of(unsigned long long inside, unsigned long long squares, int64_t entries) {
   return (long long)inside * (long long)entries - (long long)squares;
 }
@@ -58,7 +45,7 @@ long long score_of(unsigned long long inside, unsigned long long squares, int64_
 /// One phase on `lv`: label[] (level-local community per level vertex) and tot[] are filled.
 /// Returns GRX_OK and sets `kept_any`.
 template <bool W>
-int run_phase(grx_context_s* ctx, grx_graph_s* pattern, level_t& lv, const limits_t& lim, int64_t E,
+int run_phase(grx_context_s* ctx, grx_graph_s* pattern, level_t& lv, const sweep_limits_t& lim, int64_t E,
               call_clock_t& clock, tally_t& tally, hip::device_array_t<int32_t>& label_out,
               hip::device_array_t<int32_t>& tot_out, bool& kept_any) {
   auto& sc = ctx->single();
@@ -66,149 +53,29 @@ int run_phase(grx_context_s* ctx, grx_graph_s* pattern, level_t& lv, const limit
   const int32_t n = lv.n;
   kept_any = false;
 
-  k::lpa_key_t key{nullptr, lv.ap, {0, 0, 0}};
-  key.b[0] = std::min(k::LPA_SMALL_ROW, lim.big_row);
-  key.b[1] = std::min(k::LPA_WAVE_ROW, lim.big_row);
-  key.b[2] = std::max(key.b[1], std::min(lim.big_row, lim.slots / 2));  // a medium row's table never overflows
-  const int32_t medium_slots = (int32_t)k::lpa_slots_for(key.b[2], lim.slots);
-
-  // 1. the colour classes of the level's pattern CSR
-  hip::device_array_t<int32_t> color((std::size_t)n);
-  int32_t num_colors = 0;
-  if (int rc = grx_color(ctx, pattern, color.data(), &num_colors, nullptr, nullptr))
+  // 1. the colour classes of the level's pattern CSR, the vertices by (class, bin) and the plan
+  class_schedule_t sched;
+  if (int rc = sched.build(ctx, pattern, lv.ap, n, lim, clock, tally.launches, "grx_louvain"))
     return rc;
-  key.color = color.data();
-  const int32_t n_keys = num_colors * k::LPA_BINS;
-  int bits = 1;
-  while ((1ll << bits) < n_keys)
-    ++bits;
-
-  // 2. the vertices by (class, bin), ascending ids within; sizes and entry totals to the host
-  hip::device_array_t<unsigned> keys((std::size_t)n);
-  hip::device_array_t<int32_t> order((std::size_t)n), starts((std::size_t)n_keys + 1);
-  hip::device_array_t<unsigned long long> entries((std::size_t)n_keys);
-  std::vector<int32_t> h_starts((std::size_t)n_keys + 1);
-  std::vector<unsigned long long> h_entries((std::size_t)n_keys);
-  clock.begin_batch();
-  {
-    auto key_it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<int32_t>(0), key);
-    std::size_t bytes = 0;
-    GRX_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, key_it, keys.data(),
-                                            rocprim::make_counting_iterator<int32_t>(0), order.data(), (std::size_t)n, 0,
-                                            bits, s));
-    hip::device_array_t<unsigned char> temp(std::max<std::size_t>(bytes, 256));
-    GRX_HIP_CHECK(rocprim::radix_sort_pairs(temp.data(), bytes, key_it, keys.data(),
-                                            rocprim::make_counting_iterator<int32_t>(0), order.data(), (std::size_t)n, 0,
-                                            bits, s));
-    GRX_HIP_CHECK(hipMemsetAsync(entries.data(), 0, sizeof(unsigned long long) * (std::size_t)n_keys, s));
-    k::lpa_starts_kernel<<<grid_for((std::size_t)n_keys + 1, k::LPA_BLOCK, sc), k::LPA_BLOCK, 0, s>>>(
-        keys.data(), n, n_keys, starts.data());
-    k::lpa_entries_kernel<<<grid_for((std::size_t)n, k::LPA_BLOCK, sc), k::LPA_BLOCK, 0, s>>>(
-        keys.data(), order.data(), lv.ap, n, entries.data());
-    GRX_HIP_CHECK(hipGetLastError());
-    tally.launches += 3;
-    clock.end_batch();
-    GRX_HIP_CHECK(
-        hipMemcpyAsync(h_starts.data(), starts.data(), h_starts.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    GRX_HIP_CHECK(hipMemcpyAsync(h_entries.data(), entries.data(), h_entries.size() * sizeof(unsigned long long),
-                                 hipMemcpyDeviceToHost, s));
-    GRX_HIP_CHECK(hipStreamSynchronize(s));  // the sort's temporary storage is released behind it
-  }
-
-  // 3. the launch plan of a sweep, and what the overflow paths may need
-  std::vector<step_t> steps;
-  unsigned long long pool_entries = 0;
-  std::size_t over_rows = 0;
-  for (int32_t c = 0; c < num_colors; ++c) {
-    const int32_t* at = h_starts.data() + k::LPA_BINS * c;
-    const unsigned long long* e = h_entries.data() + k::LPA_BINS * c;
-    const int32_t size = at[k::LPA_BINS] - at[0];
-    if (size == 0 || e[0] + e[1] + e[2] + e[3] == 0)  // nobody, or only vertices without entries
-      continue;
-    const bool narrow =
-        lim.narrow_edges && size <= k::LPA_NARROW_VERTICES && e[0] + e[1] + e[2] + e[3] <= lim.narrow_edges;
-    if (narrow) {
-      pool_entries = std::max(pool_entries, e[2] + e[3]);  // at least its longest row
-      if (!steps.empty() && steps.back().narrow && steps.back().c1 == c)
-        steps.back().c1 = c + 1;
-      else
-        steps.push_back({c, c + 1, true});
-    } else {
-      pool_entries = std::max(pool_entries, e[3]);
-      over_rows = std::max<std::size_t>(over_rows, (std::size_t)(at[4] - at[3]));
-      steps.push_back({c, c + 1, false});
-    }
-  }
-  error::throw_if_exception(pool_entries > (unsigned long long)INT32_MAX, "grx_louvain: more entries than a CSR holds");
 
   hip::device_array_t<int32_t> label((std::size_t)n), before((std::size_t)n), tot((std::size_t)n),
       tot_before((std::size_t)n);
-  hip::device_array_t<int32_t> pool(4 * (std::size_t)pool_entries + 4);
-  hip::device_array_t<unsigned long long> over(over_rows + 1);
-  hip::device_array_t<int2> big(2 * ((std::size_t)lv.entries / k::LPA_INSIDE_SEGMENT) + 1);
+  hip::device_array_t<int2> big(big_list_size(lv.entries));
   hip::device_array_t<k::louvain_counters_t> counters(1);
   k::louvain_counters_t* ctr = counters.data();
   if (!W)
     lv.k = hip::device_array_t<int32_t>((std::size_t)n);
   const k::louvain_state_t st{lv.ap, lv.aj, lv.aw, lv.k.data(), label.data(), before.data(), tot.data(), (long long)E};
 
-  const std::size_t medium_lds = 2 * sizeof(int32_t) * (std::size_t)medium_slots;
-  const std::size_t big_lds = 2 * sizeof(int32_t) * (std::size_t)lim.slots;
-  const std::size_t narrow_lds =
-      std::max(big_lds, 2 * sizeof(int32_t) * (std::size_t)k::LPA_WAVE_SLOTS * (k::LPA_BIG_BLOCK / hip::wave_size));
-  GRX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k::louvain_block_kernel<k::LPA_BLOCK, W>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)medium_lds));
-  GRX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k::louvain_block_kernel<k::LPA_BIG_BLOCK, W>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)big_lds));
-  GRX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k::louvain_narrow_kernel<W>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)narrow_lds));
-
-  auto wide = [&](int32_t c) {
-    const int32_t* at = h_starts.data() + k::LPA_BINS * c;
-    const int32_t* rows = order.data();
-    if (const int32_t r = at[1] - at[0]) {
-      k::louvain_group_kernel<k::LPA_SMALL, W>
-          <<<grid_for((std::size_t)r, k::LPA_BLOCK / k::LPA_SMALL, sc), k::LPA_BLOCK, 0, s>>>(st, rows + at[0], r);
-      ++tally.launches;
-    }
-    if (const int32_t r = at[2] - at[1]) {
-      k::louvain_group_kernel<hip::wave_size, W>
-          <<<grid_for((std::size_t)r, k::LPA_BLOCK / hip::wave_size, sc), k::LPA_BLOCK, 0, s>>>(st, rows + at[1], r);
-      ++tally.launches;
-    }
-    if (const int32_t r = at[3] - at[2]) {
-      k::louvain_block_kernel<k::LPA_BLOCK, W><<<grid_for((std::size_t)r, 1, sc), k::LPA_BLOCK, medium_lds, s>>>(
-          st, rows + at[2], r, medium_slots, over.data(), ctr);
-      ++tally.launches;
-    }
-    if (const int32_t r = at[4] - at[3]) {
-      // the class's overflow list and its share of the pool start empty
-      GRX_HIP_CHECK(hipMemsetAsync(&ctr->overflow_n, 0, 2 * sizeof(int), s));
-      k::louvain_block_kernel<k::LPA_BIG_BLOCK, W><<<grid_for((std::size_t)r, 1, sc), k::LPA_BIG_BLOCK, big_lds, s>>>(
-          st, rows + at[3], r, lim.slots, over.data(), ctr);
-      k::louvain_fallback_kernel<W>
-          <<<std::min<unsigned>((unsigned)r, (unsigned)sc.compute_units()), k::LPA_BIG_BLOCK, 0, s>>>(
-              st, over.data(), pool.data(), ctr);
-      tally.launches += 2;
-    }
-    // the class is decided: its moves reach tot
-    const int32_t r = at[4] - at[0];
-    k::louvain_apply_kernel<<<grid_for((std::size_t)r, k::LPA_BLOCK, sc), k::LPA_BLOCK, 0, s>>>(st, rows + at[0], r, ctr);
-    ++tally.launches;
-  };
-  auto enqueue_score = [&] {
-    const unsigned grid = grid_for((std::size_t)n, k::LPA_BLOCK, sc);
-    k::louvain_inside_kernel<W><<<grid, k::LPA_BLOCK, 0, s>>>(lv.ap, lv.aj, lv.aw, label.data(), n, big.data(), ctr);
-    k::louvain_inside_big_kernel<W><<<(unsigned)sc.compute_units() * 4, k::LPA_BLOCK, 0, s>>>(
-        lv.ap, lv.aj, lv.aw, label.data(), big.data(), ctr);
-    k::louvain_squares_kernel<<<grid, k::LPA_BLOCK, 0, s>>>(tot.data(), n, ctr);
-    tally.launches += 3;
+  using decision_t = k::louvain_decision_t<W>;
+  auto score = [&] {
+    tally.launches += enqueue_score<W>(sc, lv.ap, lv.aj, lv.aw, label.data(), n, tot.data(), big.data(), ctr);
   };
   auto publish = [&](unsigned long long* mirror, int slot, unsigned long long seq) {
     k::louvain_publish_kernel<<<1, 64, 0, s>>>(ctr, mirror, slot, seq);
   };
 
-  // 4. label[v] = v, tot[v] = k(v); the first phase scores that partition, the later ones inherit
+  // 2. label[v] = v, tot[v] = k(v); the first phase scores that partition, the later ones inherit
   // the score: aggregation changes neither E nor N
   GRX_HIP_CHECK(hipMemsetAsync(ctr, 0, sizeof *ctr, s));
   clock.begin_batch();
@@ -216,7 +83,7 @@ int run_phase(grx_context_s* ctx, grx_graph_s* pattern, level_t& lv, const limit
       lv.ap, lv.k.data(), label.data(), tot.data(), n);
   ++tally.launches;
   if (!tally.scored) {
-    enqueue_score();
+    score();
     const unsigned long long* m = hand_off(sc, clock, publish);
     ++tally.launches;
     tally.inside = m[k::LOUVAIN_INSIDE];
@@ -225,23 +92,15 @@ int run_phase(grx_context_s* ctx, grx_graph_s* pattern, level_t& lv, const limit
     clock.begin_batch();
   }
 
-  // 5. sweeps until one moves nothing or fails to raise the score
+  // 3. sweeps until one moves nothing or fails to raise the score
   const std::size_t bytes = sizeof(int32_t) * (std::size_t)n;
   for (int32_t sweeps = 0;; ++sweeps) {
     // N rises by at least 1 per kept sweep and is at most E^2: more is a fault of the kernels
     error::throw_if_exception(sweeps > 100000, "grx_louvain: more sweeps than a phase can keep");
     GRX_HIP_CHECK(hipMemcpyAsync(before.data(), label.data(), bytes, hipMemcpyDeviceToDevice, s));
     GRX_HIP_CHECK(hipMemcpyAsync(tot_before.data(), tot.data(), bytes, hipMemcpyDeviceToDevice, s));
-    for (const step_t& step : steps) {
-      if (step.narrow) {
-        k::louvain_narrow_kernel<W><<<1, k::LPA_BIG_BLOCK, narrow_lds, s>>>(st, order.data(), starts.data(), step.c0,
-                                                                          step.c1, lim.slots, pool.data(), ctr);
-        ++tally.launches;
-      } else {
-        wide(step.c0);
-      }
-    }
-    enqueue_score();
+    enqueue_sweep<decision_t>(sc, sched, st, ctr, tally.launches);
+    score();
     const unsigned long long* m = hand_off(sc, clock, publish);
     ++tally.launches;
     tally.expanded += lv.entries;
@@ -376,19 +235,7 @@ extern "C" int grx_louvain(grx_context_t ctx, grx_graph_t g, int32_t* d_communit
     auto& sc = ctx->single();
     const hipStream_t s = sc.stream();
 
-    // test hooks: the row length above which a row gets 1024 threads and the largest table, the
-    // entries a class may have to run in the one-workgroup kernel (0 sends every class to the wide
-    // kernels), and the slots of the largest LDS table
-    limits_t lim;
-    lim.big_row = (int32_t)env_or("GRX_LOUVAIN_BIG_ROW", k::LPA_BIG_ROW, 1, INT32_MAX);
-    lim.narrow_edges = (unsigned long long)env_or("GRX_LOUVAIN_NARROW_EDGES", k::LPA_NARROW_EDGES, 0, 1ll << 30);
-    {
-      int dev = 0, max_lds = 0;
-      GRX_HIP_CHECK(hipGetDevice(&dev));
-      GRX_HIP_CHECK(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-      const long long most = ((long long)max_lds - 1024) / 8;  // a key and a sum; the static part stays below 1 KB
-      lim.slots = (int32_t)env_or("GRX_LOUVAIN_LDS_SLOTS", most, k::LPA_MIN_SLOTS, most);
-    }
+    const sweep_limits_t lim = sweep_limits("GRX_LOUVAIN");  // the test hooks and the LDS the device allows
 
     call_clock_t clock(s, timed);
     clock.start();
@@ -452,9 +299,7 @@ extern "C" int grx_louvain(grx_context_t ctx, grx_graph_t g, int32_t* d_communit
     if (h_communities)
       *h_communities = (int64_t)communities;
     if (h_modularity)
-      *h_modularity = g->nnz == 0 ? 0.0
-                                  : (double)tally.inside / (double)g->nnz -
-                                        (double)tally.squares / ((double)g->nnz * (double)g->nnz);
+      *h_modularity = modularity_of(tally.inside, tally.squares, g->nnz);
     if (h_levels)
       *h_levels = levels;
     if (stats) {

@@ -112,6 +112,8 @@ SHAPES = {
     "k300_pendants": lambda: (1300, _clique(300) + [(i % 300, 300 + i) for i in range(1000)]),
     "shuffled_path": _shuffled_path, "grid": _grid, "triangles": _triangles,
     "hub_of_cliques": _hub_of_cliques,
+    # 200 isolated vertices around a triangle: every class but the first holds connected vertices only
+    "triangle_among_isolated": lambda: (203, [(1, 100), (100, 202), (202, 1)]),
 }
 
 
@@ -145,6 +147,8 @@ def test_known_answers_and_shapes_that_stress_the_schedule(ea, ctx, name):
         assert c.tolist() == [0, 1, 2, 3, 3, 5]
     if name == "no_entries":
         assert c.tolist() == list(range(9)) and st.iterations == 1 and st.edges_expanded == 0 and want[3] == 1
+    if name == "triangle_among_isolated":
+        assert want[1] == 201 and (c[[1, 100, 202]] == 1).all()
     if name == "triangles":
         assert (c.reshape(-1, 3) == c.reshape(-1, 3)[:, :1]).all() and (c[::3] == np.arange(0, 150000, 3)).all()
     if name == "shuffled_path":

@@ -100,6 +100,8 @@ SHAPES = {
     "star_hub_first": lambda: _star(False), "star_hub_last": lambda: _star(True),
     "k300_pendants": lambda: (1300, _clique(300) + [(i % 300, 300 + i) for i in range(1000)]),
     "shuffled_path": _shuffled_path, "grid": _grid, "triangles": _triangles,
+    # 200 isolated vertices around a triangle: every class but the first holds connected vertices only
+    "triangle_among_isolated": lambda: (203, [(1, 100), (100, 202), (202, 1)]),
 }
 
 
@@ -129,6 +131,8 @@ def test_known_answers_and_shapes_that_stress_the_schedule(ea, ctx, name):
         assert c.tolist() == list(range(9)) and st.iterations == 1 and st.edges_expanded == 0
     if name == "repeats_decide":
         assert c[3] == c[4] and c[3] != c[2]
+    if name == "triangle_among_isolated":
+        assert want[1] == 201 and st.iterations == 2 and (c[[1, 100, 202]] == 1).all()
     if name == "triangles":
         assert (c.reshape(-1, 3) == c.reshape(-1, 3)[:, :1]).all() and (c[::3] == np.arange(0, 150000, 3)).all()
 
