@@ -95,14 +95,23 @@ int essentials_amd::ensure_can_pull(grx_context_s* ctx, grx_graph_s* g) {
 
 grx_graph_s* essentials_amd::hot_copy(grx_context_s* ctx, grx_graph_s* g, bool csr_only) {
   std::lock_guard<std::mutex> lock(g->hot_mutex);
+  if (g->in_edges && g->hot && g->hot->weight_symmetric) {
+    // in-edges attached after the copy was made: the caller says "directed", the equal-weights
+    // verdict is withdrawn and the rows sorted for it (8 bytes per edge) go with it
+    std::lock_guard<std::mutex> copy_lock(g->hot->hot_mutex);
+    g->hot->weight_symmetric = false;
+    g->hot->light.release();
+  }
   if (g->in_edges && !csr_only)
     return nullptr;  // attached after the copy was made: the copy has no transpose
   // The copy carries no transpose.  Its view may pass its CSR off as its own in-rows only when that
   // is KNOWN to be true: a caller that attached in-edges says the graph is directed, and nobody
   // has compared the CSR with its transpose then (ensure_can_pull returns before it would).
   const int copy_symmetry = g->in_edges ? (int)grx_graph_s::asymmetric : g->symmetry;
+  const bool copy_weight_symmetric = g->weight_symmetric && !g->in_edges;
   if (g->hot) {
     g->hot->symmetry = copy_symmetry;  // may have been verified, or in-edges attached, since
+    g->hot->weight_symmetric = copy_weight_symmetric;
     return g->hot_first == 0 ? nullptr : g->hot.get();
   }
   int want = g->hot_first;
@@ -129,6 +138,7 @@ grx_graph_s* essentials_amd::hot_copy(grx_context_s* ctx, grx_graph_s* g, bool c
   h->max_degree = g->max_degree;
   h->max_degree_known = true;
   h->symmetry = copy_symmetry;  // renumbering keeps (a)symmetry
+  h->weight_symmetric = copy_weight_symmetric;  // ... and every edge its weight
   h->hot_first = 0;           // a copy has no copy of its own
   {  // descending degree order: the vertices with edges come first -- how many are there?
     const int32_t* hap = h->d_ap;
@@ -328,8 +338,10 @@ int grx_graph_from_mtx(const char* path, grx_graph_t* out) {
                                      csr.row_offsets.data(), csr.column_indices.data(),
                                      csr.nonzero_values.data(), out);
     // a "symmetric" file is expanded to both directions by the loader: its own transpose
-    if (rc == GRX_OK && mm.scheme == io::symmetric)
+    if (rc == GRX_OK && mm.scheme == io::symmetric) {
       (*out)->symmetry = grx_graph_s::symmetric;
+      (*out)->weight_symmetric = true;  // ... with the entry's one value
+    }
     return rc;
   });
 }

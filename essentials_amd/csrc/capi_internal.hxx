@@ -98,6 +98,8 @@ struct grx_graph_s {
     ap.set_parking(false);
     aj.set_parking(false);
     ax.set_parking(false);
+    light.records.set_parking(false);
+    light.lightest.set_parking(false);
   }
   int32_t n_rows = 0, n_cols = 0;
   int64_t nnz = 0;
@@ -118,6 +120,31 @@ struct grx_graph_s {
   // PULL traversal asks (essentials_amd::ensure_can_pull)
   enum symmetry_t { symmetry_unknown = 0, symmetric = 1, asymmetric = 2 };
   mutable int symmetry = symmetry_unknown;
+  // ... and with EQUAL WEIGHTS in the two directions of every pair?  Only the two builders that emit
+  // both directions of a pair with one weight say so (grx_graph_rmat with symmetrize, grx_graph_from_mtx
+  // on a symmetric file); the renumbered copy inherits it.  ensure_can_pull's verdict is structural
+  // and never sets it.  What grx_sssp asks before it pulls a round.
+  bool weight_symmetric = false;
+  // The rows of this handle's CSR sorted by ascending weight, for grx_sssp's pulled rounds
+  // (advance_kernels.hxx: sssp_pull_kernel): one 8-byte {neighbour, weight} record per edge under the
+  // handle's own row offsets, and the first weight of every row.  Built on first use under hot_mutex
+  // (essentials_amd::light_rows, capi_sssp.hip), released with the handle or when the verdict above is
+  // withdrawn.  `ready`: set once a build has COMPLETED -- the arrays are empty until then, and a build
+  // that throws leaves the handle as it was; `refused`: a weight is NaN, no further build is tried.
+  struct light_rows_s {
+    gunrock::hip::device_array_t<unsigned long long> records;
+    gunrock::hip::device_array_t<float> lightest;
+    bool ready = false, refused = false;
+    float build_ms = 0;
+    void release() {
+      records = gunrock::hip::device_array_t<unsigned long long>();
+      lightest = gunrock::hip::device_array_t<float>();
+      records.set_parking(false);
+      lightest.set_parking(false);
+      ready = refused = false;
+      build_ms = 0;
+    }
+  } light;
   // Hot-first renumbered copy (include/gunrock/graph/reorder.hxx) that grx_bfs / grx_sssp run on;
   // labels are delivered in the caller's numbering.  -1: automatic (GRX_HOT_FIRST, size), 0: off,
   // 1: on (grx_graph_hot_first).
@@ -165,6 +192,11 @@ struct grx_graph_s {
 };
 
 namespace essentials_amd {
+
+/// The weight-sorted rows of `g` (grx_graph_s::light), built on first use; nullptr when `g` is not
+/// known to be its own transpose with equal weights, or holds a NaN weight (capi_sssp.hip).  Call
+/// inside guarded().
+const grx_graph_s::light_rows_s* light_rows(grx_context_s* ctx, grx_graph_s* g);
 
 /// A test hook: the integer in environment variable `name` clamped to [lo, hi]; `fallback` when unset.
 inline long long env_or(const char* name, long long fallback, long long lo, long long hi) {

@@ -605,6 +605,12 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
   hip::device_array_t<unsigned char> pend;
   hip::device_array_t<unsigned long long> near_bins;
   hip::device_array_t<unsigned> near_threshold;
+  // Pulled rounds (sssp_enactor_t::pull_round): the weight-sorted rows of the handle the run is on
+  // (empty: this run never pulls), and the two words the selection passes reduce the lowest
+  // distance bits of the pending set into, in turn -- a round reads the word of the selection
+  // that built its frontier while that selection's chooser has re-armed the other one.
+  operators::advance::pull::light_rows_t light_rows;
+  hip::device_array_t<unsigned> near_lowest;
   // renumbered graph (see bfs_problem_t): distances are delivered as distance[scatter_to[v]], or
   // gathered through the inverse permutation when the owner has it on the device
   const vertex_t* scatter_to = nullptr;
@@ -654,6 +660,10 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
       near_bins.resize(hip::kernels::NEAR_BINS);
       near_threshold.resize(1);
     }
+    if (!near_far)
+      light_rows = operators::advance::pull::light_rows_t();
+    if (light_rows)
+      near_lowest.resize(2);
   }
   /// bound16[v] <- ceil16(ordered bits of the current distance): one pass, on the context's stream.
   void snapshot_bounds() {
@@ -679,6 +689,8 @@ struct sssp_problem_t : gunrock::problem_t<graph_t> {
       pend.zero(ctx->stream());
       near_bins.zero(ctx->stream());
     }
+    if (light_rows)
+      GRX_HIP_CHECK(hipMemsetAsync(near_lowest.data(), 0xff, 2 * sizeof(unsigned), ctx->stream()));
     if (packed_labels) {
       unsigned long long* p = packed.data();
       const unsigned long long zero = (unsigned long long)ordered_bits(weight_t(0)) << 32;
@@ -758,6 +770,13 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
   double near_frac = 0.33;                 // share of the pending work one round takes (profiles/sssp_near_ab.txt)
   unsigned long long deferred_work = 0;    // work of what the last selection left pending
   bool input_is_near = false;              // select_near() built the input frontier
+  // Pulled rounds: a scanning wide round whose frontier a selection built is
+  // pulled over the weight-sorted rows when its work exceeds pull_alpha x the degree sum of the
+  // vertices still unreached (GRX_SSSP_PULL=0 / GRX_SSSP_PULL_ALPHA; profiles/sssp_pull_ab.txt)
+  double pull_alpha = 0.5;                 // lowest mean enact() of the swept {0.5, 1, 2, 4}, six RMAT-22 sources (0: no cost bound)
+  unsigned selections = 0;                 // select_near() calls of this run: which word holds dmin
+  unsigned long long unreached_work = 0;   // degree sum of the unreached ids the last selection saw
+  int pull_iterations = 0;
 
   sssp_enactor_t(problem_type* p, std::shared_ptr<gcuda::multi_context_t> ctx,
                  enactor_properties_t props = enactor_properties_t())
@@ -840,9 +859,9 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
     const unsigned* threshold = P->near_threshold.data();
     // pass 1: the bounds as scan_improved() leaves them, pend |= lowered in this round, and the
     // pending work by distance code
-    auto visit = [packed, this_round, bound16, pend] __device__(vertex_t const& v) -> int {
+    auto visit = [packed, this_round, bound16, pend] __device__(vertex_t const& v, unsigned& bits) -> int {
       const unsigned long long label = packed[v];
-      const unsigned bits = (unsigned)(label >> 32);
+      bits = (unsigned)(label >> 32);
       const unsigned up = (bits >> 16) + ((bits & 0xffffu) ? 1u : 0u);
       const unsigned b = up > 0xffffu ? 0xffffu : up;
       bound16[v] = (unsigned short)b;
@@ -856,8 +875,12 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
     const unsigned long long min_total =
         std::max(ctx->options().sssp_near_min_work, ctx->options().label_scan_min_work);
     hip::clocked_t clock(*ctx);  // select_range below stops it: one interval for the three kernels
+    // ... and, for a run that may pull, the lowest pending distance and the unreached work
+    unsigned* lowest = P->light_rows ? P->near_lowest.data() + (selections & 1u) : nullptr;
+    unsigned* rearm = P->light_rows ? P->near_lowest.data() + ((selections + 1u) & 1u) : nullptr;
     operators::filter::choose_near(G, n_scan, visit, P->near_bins.data(), P->near_threshold.data(), min_total,
-                                   near_frac, *ctx);
+                                   near_frac, *ctx, lowest,
+                                   problem_type::ordered_bits(std::numeric_limits<weight_t>::max()), rearm);
     // pass 2: the near part leaves the pending set
     auto near = [bound16, pend, threshold] __device__(vertex_t const& v) -> bool {
       if (!pend[v] || k::near_code(bound16[v]) > *threshold)
@@ -877,6 +900,8 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
     const unsigned long long total = ctx->workspace().mirror()[hip::kernels::C_PENDING];
     const unsigned long long taken = E->get_output_frontier()->work_hint();
     deferred_work = total > taken ? total - taken : 0ull;
+    unreached_work = ctx->workspace().mirror()[hip::kernels::C_FAR_WORK];
+    ++selections;
     E->swap_frontier_buffers();
     input_is_near = true;
     if (debug) {
@@ -912,10 +937,48 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
     select_near(packed, 0xffffffffu, context);
   }
 
+  /// Form P: a round that would push as a scanning wide form (B, D, E with scan) is pulled instead --
+  /// every vertex that an edge of weight w from a frontier vertex could still improve reads its
+  /// weight-sorted row from the front and stops where fl(dmin + w) reaches its label
+  /// (advance_kernels.hxx: sssp_pull_kernel).  Taken when the run has the rows
+  /// (a graph known to be its own transpose with equal weights), a selection built the input
+  /// frontier -- its passes left dmin, the lowest pending distance, and the degree sum of the
+  /// unreached vertices -- and the round's work exceeds pull_alpha x that sum.  The round tags mean
+  /// what they mean after a push round without output: scan_next() follows.  Returns false when the
+  /// round has to push.
+  bool pull_round(bool from_near, unsigned long long work, unsigned long long* packed, unsigned this_round,
+                  gcuda::multi_context_t& context) {
+    auto P = this->get_problem();
+    auto G = P->get_graph();
+    auto ctx = context.get_context(0);
+    if (!from_near || selections == 0 || !P->light_rows || !near_on(*ctx))
+      return false;
+    if (!((double)work > pull_alpha * (double)unreached_work))
+      return false;
+    note_form('P', true, false);
+    ++pull_iterations;
+    const std::size_t n_scan = G.properties.leading_connected ? (std::size_t)G.properties.leading_connected
+                                                              : (std::size_t)G.get_number_of_vertices();
+    const unsigned* dmin = P->near_lowest.data() + ((selections - 1u) & 1u);
+    const unsigned long long unreached = unreached_work;  // the selection below replaces it
+    unsigned dmin_bits = 0;
+    if (debug)  // before the next selection re-arms the word
+      GRX_HIP_CHECK(hipMemcpy(&dmin_bits, dmin, sizeof dmin_bits, hipMemcpyDeviceToHost));
+    operators::advance::pull::enqueue_sssp_range(
+        G, n_scan, P->light_rows, packed, dmin,
+        problem_type::ordered_bits(std::numeric_limits<weight_t>::max()), this_round, *ctx);
+    scan_next(packed, this_round, work, context);  // its hand-off carries C_EXAMINED
+    if (debug)
+      std::fprintf(stderr, "[grx] sssp pull: iteration %d dmin %g examined %llu unreached_work %llu\n",
+                   (int)this->iteration, (double)problem_type::from_ordered_bits(dmin_bits),
+                   ctx->workspace().mirror()[hip::kernels::C_EXAMINED], unreached);
+    return true;
+  }
+
   /// GRX_DEBUG: which form this iteration takes.  Packed labels: A plain,
   /// B label scan, C bounded, D bounded + scan, E early-live (`scan`: it ran without an output and the
-  /// label scan built the next frontier; `snapshot`: snapshot_bounds() ran first).  T: the reference's
-  /// two-pass formulation, W: distance and stamp in two words.
+  /// label scan built the next frontier; `snapshot`: snapshot_bounds() ran first), P pulled (above).
+  /// T: the reference's two-pass formulation, W: distance and stamp in two words.
   void note_form(char form, bool scan, bool snapshot) {
     if (!debug)
       return;
@@ -932,7 +995,7 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
     // Near / far selection: a wide frontier that is not yet the near part of a pending set is split
     // before it is expanded (RMAT-22: the 9 K hubs the source's iteration found, 90 M edges, most of
     // which would be expanded again one round later with better distances)
-    const bool from_near = input_is_near;
+    bool from_near = input_is_near;
     input_is_near = false;
     if (P->packed_labels && !from_near) {
       auto ctx = context.get_context(0);
@@ -941,6 +1004,7 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
           work >= ctx->options().sssp_near_min_work && work >= ctx->options().label_scan_min_work) {
         split_input(P->packed.data(), context);
         input_is_near = false;  // says how the NEXT input was built: set again if this iteration scans
+        from_near = true;
       }
     }
     P->log.note(E->get_input_frontier()->get_number_of_elements(),
@@ -1049,6 +1113,11 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
             ctx->options().settled_filter &&
             !ctx->options().holes_layout && work != frontier_t::unknown_work &&
             work >= ctx->options().settled_min_work) {
+          // while deferred work remains only a label scan can name the next frontier
+          const bool scan = deferred_work != 0 ||
+                            (ctx->options().label_scan_min_work && work >= ctx->options().label_scan_min_work);
+          if (scan && pull_round(from_near, work, packed, this_round, context))
+            return;
           const bool snapshot = !P->bounds_fresh;
           if (snapshot) {  // part of this iteration's advance: timed with it when kernels are timed
             hip::clocked_t clock(*ctx);
@@ -1066,9 +1135,6 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
             const unsigned b = bound;
             return b != 0xffffu && problem_type::ordered_bits(through) >= (b << 16);
           };
-          // while deferred work remains only a label scan can name the next frontier
-          const bool scan = deferred_work != 0 ||
-                            (ctx->options().label_scan_min_work && work >= ctx->options().label_scan_min_work);
           note_form(reached_enough ? (scan ? 'D' : 'C') : 'E', scan, snapshot);
           auto run = [&](auto hinted) {
             if (scan) {
@@ -1109,6 +1175,8 @@ struct sssp_enactor_t : gunrock::enactor_t<problem_type> {
         if (lb == load_balance_t::block_mapped && !ctx->options().holes_layout &&
             ctx->options().label_scan_min_work && work != frontier_t::unknown_work &&
             (work >= ctx->options().label_scan_min_work || deferred_work != 0)) {
+          if (pull_round(from_near, work, packed, this_round, context))
+            return;
           note_form('B', true, false);
           ctx->options().defer_sync_of_none_output = true;  // the scan below is its hand-off
           operators::advance::execute<lb, operators::advance_direction_t::forward,

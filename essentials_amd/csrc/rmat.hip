@@ -263,6 +263,7 @@ extern "C" int grx_graph_rmat(grx_context_t ctx, uint32_t scale, uint32_t edge_f
     auto g = rmat_build(ctx->single(), scale, edge_factor, seed, weight_seed, symmetrize);
     // the generator knows: symmetrised = its own transpose; raw pairs = a directed graph
     g->symmetry = symmetrize ? grx_graph_s::symmetric : grx_graph_s::asymmetric;
+    g->weight_symmetric = symmetrize != 0;  // both slots of pair k carry rmat_weight(wseed, k)
     *out = g.release();
     // the generator's sort buffers (16 B per slot: 32 GiB at scale 26) are of no use to the
     // operators: do not let them fill the frontier block cache

@@ -237,7 +237,15 @@ void grx_default_options(grx_options* opt);
 int grx_bfs(grx_context_t ctx, grx_graph_t g, int32_t source, int32_t* d_distances,
             int32_t* d_predecessors, const grx_options* opt, grx_stats* stats);
 /* sssp::run(G, source, distances, predecessors, context)  algorithms/sssp.hxx:155-185.
- * d_distances: float[V] out (FLT_MAX = unreached). */
+ * d_distances: float[V] out (FLT_MAX = unreached).
+ * On a graph KNOWN to be its own transpose with equal weights in both directions (grx_graph_rmat
+ * with symmetrize, grx_graph_from_mtx on a symmetric file; no check is ever run for this) the wide
+ * rounds that follow a near / far selection are pulled over a copy of the rows sorted by ascending
+ * weight: 8 bytes per edge and 4 per vertex on the handle, built by the first such call outside its
+ * timed part, released with the handle; not built when a weight is NaN or the graph has fewer edges
+ * than a selection needs, and a build that fails leaves the call pushing as before.  Same distances;
+ * stats.pull_iterations counts the pulled rounds.  GRX_SSSP_PULL=0 never pulls,
+ * GRX_SSSP_PULL_ALPHA (default 0.5; 0: every eligible round) sets the rule's factor. */
 int grx_sssp(grx_context_t ctx, grx_graph_t g, int32_t source, float* d_distances,
              int32_t* d_predecessors, const grx_options* opt, grx_stats* stats);
 /* pr::run(G, alpha, tol, p, context)  algorithms/pr.hxx:182-216.  d_p: float[V] out. */

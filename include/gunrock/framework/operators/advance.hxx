@@ -800,6 +800,42 @@ void enqueue_range(graph_t& G, std::size_t n, settled_snapshot_t<vertex_t> exact
   GRX_HIP_CHECK(hipGetLastError());
 }
 
+/// What sssp_pull_kernel walks: every row of the graph's own offsets as 8-byte {neighbour, weight}
+/// entries sorted by ascending weight, and the first weight of every row.
+struct light_rows_t {
+  const unsigned long long* records = nullptr;
+  const float* lightest = nullptr;
+  explicit operator bool() const { return records != nullptr && lightest != nullptr; }
+};
+
+/**
+ * @brief A wide SSSP round, pulled over the id range [0, n) of a graph that is its OWN transpose with
+ * EQUAL weights in both directions (the caller's knowledge: nothing is checked here) -- no candidate
+ * list, no output frontier, no atomics (advance_kernels.hxx: sssp_pull_kernel).  `packed`: the
+ * client's 64-bit labels (order-preserving distance bits << 32 | round tag), `dmin_bits`: a device
+ * word with the order-preserving bits of a lower bound of every frontier vertex's distance,
+ * `far_bits`: the bits of "unreached", `this_round`: the tag a lowered label gets.
+ * Only enqueues and leaves the kernel clock running: the operator that names what the round lowered
+ * is its hand-off, which also carries counter C_EXAMINED to the host.
+ */
+template <typename graph_t>
+void enqueue_sssp_range(graph_t& G, std::size_t n, light_rows_t rows, unsigned long long* packed,
+                        const unsigned* dmin_bits, unsigned far_bits, unsigned this_round,
+                        gcuda::standard_context_t& context) {
+  namespace k = detail::k;
+  using edge_t = typename graph_t::edge_type;
+  if (n == 0)
+    return;
+  error::throw_if_exception(!rows || n > (std::size_t)G.get_number_of_vertices(),
+                            "pull advance: no weight-sorted rows for this range");
+  hip::clocked_t clock(context);
+  k::sssp_pull_kernel<edge_t><<<hip::grid_for(n, k::SSSP_PULL_BLOCK, (unsigned)context.compute_units() * 8u),
+                               k::SSSP_PULL_BLOCK, 0, context.stream()>>>(
+      G.get_row_offsets(), rows.records, rows.lightest, n, packed, dmin_bits, far_bits, this_round,
+      context.workspace().counters(), (int)k::C_EXAMINED);
+  GRX_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace pull
 
 // ===========================================================================

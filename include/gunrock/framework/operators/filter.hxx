@@ -190,17 +190,23 @@ void select_range(graph_t& G, std::size_t n, pred_t pred, frontier_t& output,
  * counter C_PENDING.  `bins`: NEAR_BINS device words, zero on entry and on exit.  Only enqueues: the
  * select_range that follows on the same stream, with the predicate "pending and code <= *threshold",
  * is the hand-off.
+ * `visit(v, bits)` also hands back the order-preserving bits of v's distance.  With `lowest` not null
+ * (a client that may pull the next round) the same pass leaves *lowest <- min(*lowest, the bits of
+ * every pending v) and the degree sum of the ids whose bits are `far_bits` in counter C_FAR_WORK, which
+ * the same hand-off carries; `rearm` (the word the NEXT call reduces into) is set to 0xffffffff.
  */
 template <typename graph_t, typename visit_t>
 void choose_near(graph_t& G, std::size_t n, visit_t visit, unsigned long long* bins, unsigned* threshold, unsigned long long min_total, double frac,
-                 gcuda::standard_context_t& context) {
+                 gcuda::standard_context_t& context, unsigned* lowest = nullptr, unsigned far_bits = 0,
+                 unsigned* rearm = nullptr) {
   namespace k = ::gunrock::hip::kernels;
   using vertex_t = typename graph_t::vertex_type;
   const unsigned grid = hip::grid_for(n, k::NEAR_BLOCK, (unsigned)context.compute_units() * 2);
-  k::near_scan_kernel<vertex_t><<<grid, k::NEAR_BLOCK, 0, context.stream()>>>(G, n, visit, bins);
+  k::near_scan_kernel<vertex_t><<<grid, k::NEAR_BLOCK, 0, context.stream()>>>(
+      G, n, visit, bins, lowest, far_bits, context.workspace().counters() + k::C_FAR_WORK);
   GRX_HIP_CHECK(hipGetLastError());
   k::near_choose_kernel<0><<<1, k::NEAR_BLOCK, 0, context.stream()>>>(
-      bins, threshold, context.workspace().counters() + k::C_PENDING, min_total, frac);
+      bins, threshold, context.workspace().counters() + k::C_PENDING, min_total, frac, rearm);
   GRX_HIP_CHECK(hipGetLastError());
 }
 

@@ -68,6 +68,8 @@ enum counter_slot : int {
   C_SELECT = 6,     ///< packers (partitioned supersteps): number of selected elements
   C_BUCKET0 = 8,    ///< bucketing: small / medium queue cursors (8, 9)
   C_MAXDEG = 12,    ///< max degree reduction
+  C_EXAMINED = 14,  ///< sssp_pull_kernel: entries whose label was looked up (a GRX_SETTLED_STATS build uses it too)
+  C_FAR_WORK = 15,  ///< near / far selection: degree sum of the scanned ids still unreached (compact_kernels.hxx)
   C_TILE_POOL = 16  ///< 16..23: dynamic tile cursors, one per pool of workgroups (work_stealing)
 };
 
@@ -1783,6 +1785,131 @@ __global__ void __launch_bounds__(SET_BLOCK)
         label(row);
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// sssp_pull_kernel: a wide SSSP round on a graph that is its own transpose WITH EQUAL WEIGHTS, pulled
+// over the id range [0, n) with no candidate list, no output and no atomics.  `records` holds every
+// row of `offsets` as 8-byte {neighbour, weight} entries sorted by ascending weight, `lightest[v]`
+// the first weight of row v.  Every vertex of the round's frontier has a distance >= dmin, and float
+// addition is monotone in each argument, so an entry of weight w can lower the label `cur` of its
+// row's vertex only while fl(dmin + w) < cur: v is skipped when its lightest entry fails that test
+// (settled vertices do), and its row is left at the first entry that fails it -- the entries examined
+// are a prefix, the rest is provably no shorter.  A lowered `cur` tightens the test.  Any reached
+// neighbour gives a valid path length, so nobody asks whether u is in the frontier; labels are read
+// with relaxed agent-scope loads (a stale larger one is harmless: its owner carries this round's tag
+// and comes back in a later frontier).  Only v's owner stores v: (cur << 32) | this_round.
+// As pull_range_kernel: a lane probes at most SSSP_PULL_PROBES entries of its own row (one 128-byte
+// line), SSSP_PULL_GROUP label lookups in flight; the rows of a wavefront still open are then walked
+// by the whole wavefront, 64 entries a step, a wave-wide minimum per step and the stop test on the
+// step's first entry.  The entries whose label was looked up are counted into `counters[examined_slot]`.
+// ---------------------------------------------------------------------------
+constexpr int SSSP_PULL_BLOCK = 256;
+constexpr int SSSP_PULL_PROBES = 16;
+constexpr int SSSP_PULL_GROUP = 4;
+static_assert(SSSP_PULL_PROBES % SSSP_PULL_GROUP == 0, "a probe is whole groups");
+
+/// float <-> 32 bits whose unsigned order is the float order (sssp_problem_t::ordered_bits).
+__device__ __forceinline__ unsigned float_order_bits(float x) {
+  const unsigned b = __float_as_uint(x);
+  return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float from_float_order_bits(unsigned u) {
+  return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu));
+}
+
+template <typename edge_t>
+__global__ void __launch_bounds__(SSSP_PULL_BLOCK)
+    sssp_pull_kernel(const edge_t* __restrict__ offsets,
+                     const unsigned long long* __restrict__ records,
+                     const float* __restrict__ lightest,
+                     std::size_t n,
+                     unsigned long long* packed,
+                     const unsigned* __restrict__ dmin_bits,
+                     unsigned far_bits,
+                     unsigned this_round,
+                     unsigned long long* counters,
+                     int examined_slot) {
+  constexpr int BLOCK = SSSP_PULL_BLOCK;
+  __shared__ unsigned long long s_examined[BLOCK / wave_size];
+  const int lane = lane_id();
+  const float dmin = from_float_order_bits(*dmin_bits);
+  unsigned long long examined = 0;
+  const std::size_t n_tiles = (n + BLOCK - 1) / BLOCK;
+  for (std::size_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const std::size_t idx = tile * BLOCK + threadIdx.x;
+    unsigned cur = 0, before = 0;
+    edge_t first = 0, deg = 0;
+    if (idx < n) {
+      before = cur = (unsigned)(packed[idx] >> 32);  // only this lane writes it in this launch
+      if (float_order_bits(dmin + lightest[idx]) < cur) {
+        first = offsets[idx];
+        deg = offsets[idx + 1] - first;
+      }
+    }
+    bool open = deg > 0;
+    edge_t r = 0;
+    const edge_t stop = deg < (edge_t)SSSP_PULL_PROBES ? deg : (edge_t)SSSP_PULL_PROBES;
+    while (r < stop && open) {
+      unsigned long long rec[SSSP_PULL_GROUP], label[SSSP_PULL_GROUP];
+      bool take[SSSP_PULL_GROUP];
+#pragma unroll
+      for (int k = 0; k < SSSP_PULL_GROUP; ++k)  // past the probe's end: its last entry again, not taken
+        rec[k] = records[first + (r + k < stop ? r + k : stop - 1)];
+#pragma unroll
+      for (int k = 0; k < SSSP_PULL_GROUP; ++k) {
+        take[k] = r + k < stop && float_order_bits(dmin + __uint_as_float((unsigned)(rec[k] >> 32))) < cur;
+        label[k] = take[k] ? load_relaxed(&packed[(unsigned)rec[k]]) : ~0ull;
+      }
+#pragma unroll
+      for (int k = 0; k < SSSP_PULL_GROUP; ++k) {
+        const unsigned bits = (unsigned)(label[k] >> 32);
+        if (take[k]) {
+          ++examined;
+          if (bits != far_bits) {
+            const unsigned through =
+                float_order_bits(from_float_order_bits(bits) + __uint_as_float((unsigned)(rec[k] >> 32)));
+            cur = through < cur ? through : cur;
+          }
+        }
+      }
+      open = take[SSSP_PULL_GROUP - 1];  // the entries taken are a prefix: the row is sorted
+      r += SSSP_PULL_GROUP;
+    }
+    // open with entries left: one row after the other, the whole wavefront on each
+    unsigned long long more = __ballot(open && deg > (edge_t)SSSP_PULL_PROBES);
+    while (more) {
+      const int owner = __ffsll((long long)more) - 1;
+      more &= more - 1ull;
+      const edge_t row_first = __shfl(first, owner, wave_size);
+      const edge_t row_deg = __shfl(deg, owner, wave_size);
+      unsigned row_cur = __shfl(cur, owner, wave_size);
+      for (edge_t r0 = (edge_t)SSSP_PULL_PROBES; r0 < row_deg; r0 += wave_size) {
+        const edge_t at = r0 + lane;
+        const unsigned long long entry = at < row_deg ? records[row_first + at] : 0ull;
+        const float w = __uint_as_float((unsigned)(entry >> 32));
+        const float w_first = __shfl(w, 0, wave_size);  // lane 0's entry exists: r0 < row_deg
+        if (!(float_order_bits(dmin + w_first) < row_cur))
+          break;  // wave-uniform
+        unsigned through = 0xffffffffu;
+        if (at < row_deg && float_order_bits(dmin + w) < row_cur) {
+          ++examined;
+          const unsigned bits = (unsigned)(load_relaxed(&packed[(unsigned)entry]) >> 32);
+          if (bits != far_bits)
+            through = float_order_bits(from_float_order_bits(bits) + w);
+        }
+        through = wave_min(through);
+        row_cur = through < row_cur ? through : row_cur;
+      }
+      if (lane == owner)
+        cur = row_cur;
+    }
+    if (idx < n && cur < before)
+      store_relaxed(&packed[idx], ((unsigned long long)cur << 32) | (unsigned long long)this_round);
+  }
+  const unsigned long long total = block_sum<BLOCK>(examined, s_examined);
+  if (threadIdx.x == 0 && total)
+    atomicAdd(&counters[examined_slot], total);
 }
 
 // ---------------------------------------------------------------------------

@@ -241,29 +241,58 @@ __global__ void __launch_bounds__(SEL_BLOCK)
 //                       returns the distance code of a pending id, -1 otherwise; the degrees of
 //                       the pending ids are summed per code -- per workgroup in LDS (32-bit bins:
 //                       the caller keeps graphs of 2^32 edges and more away), flushed once per
-//                       workgroup to the 64-bit global bins;
+//                       workgroup to the 64-bit global bins.  `visit(i, bits)` also hands back the
+//                       order-preserving bits of i's distance; where the client asks (`lowest` not
+//                       null: it may pull the next round, sssp_pull_kernel) the pass leaves two more
+//                       values, both reduced per workgroup first: *lowest <- min of the pending ids'
+//                       bits (a vector atomic min), *far_work += the degrees of the ids whose bits
+//                       are `far_bits` (still unreached);
 //   near_choose_kernel  one workgroup: prefix sum over the bins, the threshold to a device word
 //                       (where the selection's predicate reads it: no host wait), the total
 //                       pending work to a counter slot the selection's hand-off carries to the
-//                       host, the bins back to zero.
+//                       host, the bins back to zero, and `rearm` (when not null: the word the NEXT
+//                       near_scan_kernel reduces its lowest bits into) back to 0xffffffff.
 // ---------------------------------------------------------------------------
 constexpr int NEAR_BLOCK = 1024;
 
 template <typename vertex_t, typename graph_t, typename visit_t>
 __global__ void __launch_bounds__(NEAR_BLOCK)
-    near_scan_kernel(graph_t G, std::size_t n, visit_t visit, unsigned long long* __restrict__ bins) {
+    near_scan_kernel(graph_t G, std::size_t n, visit_t visit, unsigned long long* __restrict__ bins,
+                     unsigned* __restrict__ lowest, unsigned far_bits, unsigned long long* __restrict__ far_work) {
   __shared__ unsigned s_bins[NEAR_BINS];
+  __shared__ unsigned s_lowest;
+  __shared__ unsigned long long s_far;
   for (int b = threadIdx.x; b < NEAR_BINS; b += NEAR_BLOCK)
     s_bins[b] = 0u;
+  if (threadIdx.x == 0) {
+    s_lowest = 0xffffffffu;
+    s_far = 0ull;
+  }
   __syncthreads();
+  unsigned low = 0xffffffffu;
+  unsigned long long far = 0;
   for (std::size_t i = blockIdx.x * (std::size_t)NEAR_BLOCK + threadIdx.x; i < n;
        i += (std::size_t)gridDim.x * NEAR_BLOCK) {
     const vertex_t v = (vertex_t)i;
-    const int code = visit(v);
+    unsigned bits = 0;
+    const int code = visit(v, bits);
     if (code >= 0 && code < NEAR_BINS) {
       const unsigned degree = (unsigned)G.get_number_of_neighbors(v);
       if (degree)
         atomicAdd(&s_bins[code], degree);
+      low = bits < low ? bits : low;
+    } else if (lowest && bits == far_bits) {
+      far += (unsigned long long)G.get_number_of_neighbors(v);
+    }
+  }
+  if (lowest) {  // the client pulls: one atomic per wavefront in LDS, one per workgroup and word in memory
+    low = wave_min(low);
+    far = wave_sum(far);
+    if (lane_id() == 0) {
+      if (low != 0xffffffffu)
+        atomicMin(&s_lowest, low);
+      if (far)
+        atomicAdd(&s_far, far);
     }
   }
   __syncthreads();
@@ -272,12 +301,18 @@ __global__ void __launch_bounds__(NEAR_BLOCK)
     if (c)
       atomicAdd(&bins[b], (unsigned long long)c);
   }
+  if (lowest && threadIdx.x == 0) {
+    if (s_lowest != 0xffffffffu)
+      atomicMin(lowest, s_lowest);
+    if (s_far)
+      atomicAdd(far_work, s_far);
+  }
 }
 
 template <int unused = 0>  // a template so that every translation unit may define it
 __global__ void __launch_bounds__(NEAR_BLOCK)
     near_choose_kernel(unsigned long long* bins, unsigned* threshold, unsigned long long* pending_work,
-                       unsigned long long min_total, double frac) {
+                       unsigned long long min_total, double frac, unsigned* rearm) {
   __shared__ unsigned long long s_waves[NEAR_BLOCK / wave_size + 1];
   constexpr int PER = NEAR_BINS / NEAR_BLOCK;  // 4 consecutive bins per thread
   unsigned long long local[PER], sum = 0;
@@ -295,6 +330,8 @@ __global__ void __launch_bounds__(NEAR_BLOCK)
     __hip_atomic_store(pending_work, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (all)
       *threshold = NEAR_ALL;
+    if (rearm)
+      __hip_atomic_store(rearm, 0xffffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (!all) {
     const int at = near_find(local, PER, before, near_target(total, frac));
