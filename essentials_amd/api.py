@@ -229,6 +229,9 @@ _SIGNATURES = {
                                 C.POINTER(_Stats)]),
     "grx_ppr": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_float, C.c_float, _VP, _VP, _VP, C.POINTER(_Options),
                           C.POINTER(_Stats)]),
+    "grx_spmv": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_hits": (C.c_int, [_VP, _VP, C.c_float, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                           C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_random_walk": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_float, C.c_float,
                                   _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_neighbor_sample": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_uint64, _VP, C.c_int64, _VP, _VP,
@@ -1030,6 +1033,80 @@ def ppr(ctx: Context, g: Graph, seeds=None, alpha: float = 0.85, tol: float = 1e
     _check(load_library().grx_ppr(ctx._h, g._h, _ptr(h), n, alpha, tol, _ptr(p) if p.numel() else None,
                                   _ptr(iterations), _ptr(residual), C.byref(o), C.byref(s)), "grx_ppr")
     return p, {"iterations": iterations[:count], "residual": residual[:count]}, Stats._from(s)
+
+
+def _float_vector(ctx: Context, t, length: int, call: str, what: str):
+    """The float32 tensor `what` of `call`: allocated when None, else checked to be a contiguous
+    tensor of `length` on the context's device."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if t is None:
+        return torch.empty(length, dtype=torch.float32, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"{call}: {what} must be a float32 torch tensor")
+    if t.dim() != 1 or t.numel() != length or not t.is_contiguous():
+        raise ValueError(f"{call}: {what} must be a contiguous tensor of {length} elements")
+    if t.device != device:
+        raise ValueError(f"{call}: {what} must live on {device}")
+    return t
+
+
+def spmv(ctx: Context, g: Graph, x, transpose: bool = False, y=None, options: Optional[Options] = None):
+    """y = A x over the graph's entries, or y = A^T x -> (float32 y on the device, Stats).
+
+    `x`: float32 contiguous tensor on the context's device, of n_cols elements (n_rows when
+    transposed); `y`: the same of n_rows (n_cols), allocated when None, overwritten in full; the two
+    must not overlap.  Every row sum has a fixed order: the same call returns identical bits, and the
+    exact value whenever float32 holds every partial sum (include/essentials_amd.h).  The transposed
+    product is a pull over in-rows: a directed graph needs its in-edges (`g.build_in_edges(ctx)`), an
+    asymmetric CSR without them and a rectangular graph raise EngineError.  The engine's stream waits
+    for what torch has enqueued, so `x` may come straight from torch work.  Options read:
+    collect_kernel_time."""
+    if x is None:
+        raise TypeError("spmv: x must be a float32 torch tensor")
+    x = _float_vector(ctx, x, g.n_rows if transpose else g.n_cols, "spmv", "x")
+    y = _float_vector(ctx, y, g.n_cols if transpose else g.n_rows, "spmv", "y")
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_spmv(ctx._h, g._h, int(bool(transpose)), _ptr(x) if x.numel() else None,
+                                   _ptr(y) if y.numel() else None, C.byref(o), C.byref(s)), "grx_spmv")
+    return y, Stats._from(s)
+
+
+def hits(ctx: Context, g: Graph, tol: float = 1e-6, hubs=None, authorities=None, normalized: bool = False,
+         options: Optional[Options] = None):
+    """HITS hub and authority scores -> (float32 hubs, float32 authorities on the device, info, Stats).
+
+    Power iteration from h = 1: authorities = in-rows times hubs, hubs = out-rows times authorities,
+    each divided by its largest magnitude; the run stops after the first iteration whose largest hub
+    change is below `tol`, or after Options.max_iterations when that is non-zero (tol <= 0 needs it).
+    Weights are read as they are.  Every sum has a fixed order: the same call returns identical bits
+    (include/essentials_amd.h).  A directed graph needs its in-edges (`g.build_in_edges(ctx)`); an
+    asymmetric CSR without them raises EngineError.  `hubs`, `authorities`: float32 contiguous
+    tensors of V on the context's device, allocated when None.  `info` = {"iterations": int,
+    "residual": float} (the last largest change).  normalized=False delivers the engine's values
+    untouched (largest entry 1); normalized=True divides each vector by its float64 sum, networkx's
+    convention (a vector that sums to 0 is left as it is).  Options read: collect_kernel_time and
+    max_iterations.  Stats.edges_traversed is 2 * nnz * iterations and Stats.vertices_reached the
+    vertices with a hub or authority value > 0."""
+    torch = _torch()
+    hubs = _float_vector(ctx, hubs, g.n_rows, "hits", "hubs")
+    authorities = _float_vector(ctx, authorities, g.n_rows, "hits", "authorities")
+    iterations = C.c_int32()
+    residual = C.c_float()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_hits(ctx._h, g._h, tol, _ptr(hubs) if hubs.numel() else None,
+                                   _ptr(authorities) if authorities.numel() else None, C.byref(iterations),
+                                   C.byref(residual), C.byref(o), C.byref(s)), "grx_hits")
+    if normalized:
+        for v in (hubs, authorities):
+            total = float(v.sum(dtype=torch.float64)) if v.numel() else 0.0
+            if total != 0.0:
+                v.copy_((v.double() / total).float())
+    return hubs, authorities, {"iterations": int(iterations.value), "residual": float(residual.value)}, Stats._from(s)
 
 
 def random_walk(ctx: Context, g: Graph, starts=None, length: int = 80, seed: int = 0, weighted: bool = False,

@@ -819,6 +819,90 @@ int grx_bfs_multi(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, in
 int grx_ppr(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds, int32_t n_seeds, float alpha,
             float tol, float* d_p, int32_t* h_iterations, float* h_residual, const grx_options* opt,
             grx_stats* stats);
+/* Sparse matrix-vector product over the handle's entries, every row sum in a fixed order.  The
+ * reference reaches its spmv.hxx only through headers (operators::neighborreduce, which this project
+ * keeps for the header-level client); this is the same product for a C or Python caller.
+ * transpose == 0: y[r] = sum over entries (r -> c, w) of row r of x[c] * w; d_x is device
+ * float[n_cols], d_y device float[n_rows]; a rectangular graph is allowed.
+ * transpose != 0: y[c] = sum over entries (r -> c, w) of x[r] * w, as a PULL over in-rows, never a
+ * scatter: with in-edges attached (grx_graph_build_in_edges) over those arrays and their values;
+ * without them over the handle's own rows when the CSR is symmetric (an unknown verdict is verified
+ * first, as for grx_ppr); an asymmetric CSR without in-edges is GRX_ERR_UNSUPPORTED and the message
+ * names grx_graph_build_in_edges.  The verdict is structural: a symmetric structure whose weights
+ * depend on the direction needs in-edges attached.  transpose != 0 with n_rows != n_cols is
+ * GRX_ERR_UNSUPPORTED.
+ * d_y is overwritten in full; an empty row gives 0.0f.  Weights are read as they are.
+ * Reproducibility: no float atomics.  The order of a row's sum is fixed by the row's layout and one
+ * constant, GRX_SPMV_SEGMENT (default 512, minimum 64; an environment variable read per call, a test
+ * hook).  A row of at most that many entries is summed by one group of 16 lanes: lane l adds entries
+ * l, l + 16, ... in order, one fused multiply-add each, starting from 0, and the 16 sums meet in a
+ * butterfly (lane l adds lane l ^ 8's, then l ^ 4's, l ^ 2's, l ^ 1's).  A longer row is cut into
+ * segments of that size, each summed the same way by a group of its own, and a second kernel adds
+ * the partial sums in segment order.  The order never depends on the grid size, the CU count or
+ * arrival order: two calls return the same bits, changing the hook may change last bits, and whenever
+ * every term and every partial sum is representable in float32 the result is the exact value.
+ * V == 0 or an empty output (no rows to write) is GRX_OK: nothing is launched, stats (when given) is
+ * zeroed.  GRX_ERR_INVALID_ARGUMENT, found on the host before anything is launched: a NULL ctx or g,
+ * a NULL d_x or d_y whose length is above 0, and [d_x, d_x + len) overlapping [d_y, d_y + len).
+ * opt may be NULL; only collect_kernel_time is read.  stats may be NULL; set: elapsed_ms,
+ * advance_kernel_ms (with collect_kernel_time), advance_launches (kernel launches), iterations = 1,
+ * edges_traversed = edges_expanded = nnz; everything else 0.
+ * The call leaves nothing on the handle but a symmetry verdict and releases its workspace when it
+ * returns: none for a graph of at most GRX_SPMV_SEGMENT entries, otherwise 32 bytes per
+ * GRX_SPMV_SEGMENT entries of the graph (the lists of long rows and their segments, and one partial
+ * sum per segment). */
+int grx_spmv(grx_context_t ctx, grx_graph_t g, int32_t transpose, const float* d_x, float* d_y,
+             const grx_options* opt, grx_stats* stats);
+/* HITS: hub and authority scores by power iteration, two pull products per iteration.  It REPLACES
+ * the reference's hits.hxx rather than wrapping it: that client does one float atomic per edge in each
+ * direction, normalises by an L2 norm and stops on bit-equality of two vectors, so it neither repeats
+ * itself nor has a stable answer.  Here, with weights read as they are, h_0 = 1 at
+ * every vertex and for t = 1, 2, ...
+ *   y[v] = sum over in-entries  (u -> v, w) of h_{t-1}[u] * w;  a_t = y / max_v |y[v]|
+ *   z[u] = sum over out-entries (u -> v, w) of a_t[v] * w;      h_t = z / max_u |z[u]|
+ *   residual_t = max_v |h_t[v] - h_{t-1}[v]|
+ * where a vector whose largest magnitude is 0 stays all 0.  The division is carried out as a
+ * multiplication by the rounded reciprocal of the maximum, the same arithmetic wherever a value is
+ * used or delivered: the largest entry of a delivered vector is 1 to within that one rounding, and
+ * exactly 1 when the maximum is a power of two.  Rescaling to sum 1 (networkx) or to L2 norm 1 (the
+ * reference) is the caller's arithmetic.
+ * Stop: after the first t >= 1 with residual_t < tol (grx_pagerank's and grx_ppr's test), and after
+ * opt->max_iterations iterations when that is non-zero.  tol <= 0 means "never by tol";
+ * max_iterations must then be > 0.  A run that is never below tol (NaN weights) ends with
+ * GRX_ERR_RUNTIME after 2^20 iterations.
+ * d_hub, d_authority: device float[V] out, overwritten; either may be NULL, not both when V > 0, and
+ * leaving one out does not change a bit of the other.  h_iterations (HOST int32, may be NULL): t.
+ * h_residual (HOST float, may be NULL): the last residual_t.
+ * Reproducibility: a maximum and a largest difference are the same bits in any reduction order, so
+ * the iteration is order-free except its row sums, and those follow the rule of grx_spmv with the
+ * same constant GRX_SPMV_SEGMENT: no float atomics, the same call returns the same bits, and where
+ * every term and every partial sum is representable in float32 the result is the exact value.
+ * Which edges (grx_ppr's rule): with in-edges attached the in-product runs over those arrays and
+ * their values and the out-product over the rows.  Without them the rows serve both products when
+ * the CSR is symmetric (an unknown verdict is verified first); an asymmetric CSR without in-edges is
+ * GRX_ERR_UNSUPPORTED and the message names grx_graph_build_in_edges.  The verdict is structural: a
+ * caller whose symmetric structure carries direction-dependent weights attaches in-edges.
+ * Errors, all found on the host before anything is launched, GRX_ERR_INVALID_ARGUMENT: a NULL ctx or
+ * g, both outputs NULL with V > 0, n_rows != n_cols, a NaN tol, tol <= 0 with max_iterations == 0,
+ * max_iterations < 0.  V == 0 is GRX_OK: nothing is written, nothing is launched.  A graph without
+ * entries follows the definition: a_1 = h_1 = 0, residual_1 = 1, residual_2 = 0.
+ * opt may be NULL; collect_kernel_time and max_iterations are read, everything else is ignored.
+ * Method: the products y and z are kept unnormalised and the scale is applied where the next product
+ * gathers a value, so normalising costs no pass of its own; the residual is one pass over two
+ * vectors, left out in the iterations whose residual nobody reads (tol <= 0, all but the last).  With
+ * tol > 0 there is one host hand-off per iteration; with tol <= 0 the whole run is enqueued without
+ * a host wait and the figures are read once at the end.
+ * stats may be NULL; set: elapsed_ms, advance_kernel_ms (with collect_kernel_time),
+ * advance_launches (kernel launches), iterations = t, edges_traversed = edges_expanded =
+ * 2 * nnz * t, vertices_reached (the vertices with hub > 0 or authority > 0, counted from the
+ * delivered values); everything else 0.
+ * The call builds and uses no hot-first copy, leaves nothing on the handle but a symmetry verdict
+ * ensure_can_pull may have produced, and releases its workspace when it returns: 12 bytes per vertex
+ * (y and two z) and, for a graph of more than GRX_SPMV_SEGMENT entries, 32 bytes per
+ * GRX_SPMV_SEGMENT entries of the graph (the lists of long rows and their segments, 8 bytes per
+ * long row and 12 per segment at most), twice with in-edges attached. */
+int grx_hits(grx_context_t ctx, grx_graph_t g, float tol, float* d_hub, float* d_authority,
+             int32_t* h_iterations, float* h_residual, const grx_options* opt, grx_stats* stats);
 /* Random walks: first-order uniform and weighted walks and node2vec (second-order, by rejection),
  * the corpus of DeepWalk / node2vec and of random-walk samplers.  No reference counterpart.  Every
  * draw comes from a counter-based generator, so the answer is a function of the CSR and the arguments
