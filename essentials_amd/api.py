@@ -232,6 +232,10 @@ _SIGNATURES = {
     "grx_spmv": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_hits": (C.c_int, [_VP, _VP, C.c_float, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_bfs_predecessors": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_sssp_predecessors": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64), C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_random_walk": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_float, C.c_float,
                                   _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_neighbor_sample": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_uint64, _VP, C.c_int64, _VP, _VP,
@@ -1107,6 +1111,80 @@ def hits(ctx: Context, g: Graph, tol: float = 1e-6, hubs=None, authorities=None,
             if total != 0.0:
                 v.copy_((v.double() / total).float())
     return hubs, authorities, {"iterations": int(iterations.value), "residual": float(residual.value)}, Stats._from(s)
+
+
+def predecessors(ctx: Context, g: Graph, source: int, labels, predecessors=None, hops: bool = False,
+                 options: Optional[Options] = None):
+    """The shortest-path tree that finished labels imply -> (int32 predecessors on the device, int32
+    hops on the device or None, {"orphans": int, "violations": int}, Stats).
+
+    `labels`: what `bfs` (int32 depths) or `sssp` (float32 distances) delivered from `source`, a
+    contiguous tensor of V on the context's device; the dtype selects grx_bfs_predecessors or
+    grx_sssp_predecessors.  predecessors[v] is the smallest u with an entry (u, v, w) such that
+    label[u] + 1 == label[v] (BFS) or label[u] + w == label[v] as one float32 add with label[u] <
+    label[v] (SSSP); `source` for the source, -1 for an unreached vertex, -2 for an orphan (a reached
+    vertex without such an entry: behind a zero or absorbed weight).  `violations` counts the entries
+    with label[u] + w < label[v]: 0 exactly when the labels are a fixed point of relaxation, so the
+    call doubles as a check of a result (include/essentials_amd.h has the definition).
+    `predecessors`: int32 contiguous tensor of V on the context's device, allocated when None.
+    `hops` (float32 labels only; True, or such an int32 tensor): the steps from each vertex to the
+    source along the tree, -1 where the chain does not reach it; for int32 labels the depth is that
+    number and hops=True raises ValueError.  The same call returns identical tensors.  Options read:
+    collect_kernel_time.  Stats.pull_iterations is 1 when the pass walked in-rows and
+    Stats.iterations the doubling rounds that `hops` took."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in (torch.int32, torch.float32):
+        raise TypeError("predecessors: labels must be an int32 or a float32 torch tensor")
+    if labels.dim() != 1 or labels.numel() != g.n_rows or not labels.is_contiguous():
+        raise ValueError(f"predecessors: labels must be a contiguous tensor of {g.n_rows} elements")
+    if labels.device != device:
+        raise ValueError(f"predecessors: labels must live on {device}")
+    weighted = labels.dtype == torch.float32
+    if hops is not None and hops is not False and not weighted:
+        raise ValueError("predecessors: hops along a BFS tree are the depths; hops needs float32 labels")
+    predecessors = _vertex_output(ctx, g, predecessors, "predecessors", "predecessors")
+    if hops is None or hops is False:
+        hops = None
+    else:
+        hops = _vertex_output(ctx, g, None if hops is True else hops, "predecessors", "hops")
+    orphans, violations = C.c_int64(), C.c_int64()
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    lib = load_library()
+    nonempty = g.n_rows > 0
+    if weighted:
+        _check(lib.grx_sssp_predecessors(ctx._h, g._h, source, _ptr(labels) if nonempty else None,
+                                         _ptr(predecessors) if nonempty else None,
+                                         _ptr(hops) if nonempty and hops is not None else None, C.byref(orphans),
+                                         C.byref(violations), C.byref(o), C.byref(s)), "grx_sssp_predecessors")
+    else:
+        _check(lib.grx_bfs_predecessors(ctx._h, g._h, source, _ptr(labels) if nonempty else None,
+                                        _ptr(predecessors) if nonempty else None, C.byref(orphans),
+                                        C.byref(violations), C.byref(o), C.byref(s)), "grx_bfs_predecessors")
+    return predecessors, hops, {"orphans": int(orphans.value), "violations": int(violations.value)}, Stats._from(s)
+
+
+def path(predecessors, target: int) -> list:
+    """The vertices from the source to `target`, both ends included, along `predecessors` (a torch
+    tensor or a numpy array as `predecessors` returns it; copied to the host and walked there).  []
+    when the chain from `target` does not end at a vertex that is its own predecessor: `target` is
+    unreached, an orphan, behind one, or out of range.  At most V steps are made."""
+    p = predecessors.detach().cpu().numpy() if hasattr(predecessors, "detach") else np.asarray(predecessors)
+    n, v = len(p), int(target)
+    if not 0 <= v < n:
+        return []
+    walked = [v]
+    for _ in range(n):
+        u = int(p[v])
+        if u == v:
+            return walked[::-1]
+        if not 0 <= u < n:
+            return []
+        walked.append(u)
+        v = u
+    return []
 
 
 def random_walk(ctx: Context, g: Graph, starts=None, length: int = 80, seed: int = 0, weighted: bool = False,

@@ -233,11 +233,13 @@ int grx_graph_copy_to_host(grx_graph_t g, int32_t* h_row_offsets, int32_t* h_col
 void grx_default_options(grx_options* opt);
 /* bfs::run(G, source, distances, predecessors, context)  algorithms/bfs.hxx:151-176.
  * d_distances: int32[V] out (INT32_MAX = unreached). d_predecessors: unused by the reference
- * ("@todo", bfs.hxx:28), may be NULL. */
+ * ("@todo", bfs.hxx:28), may be NULL, never written: grx_bfs_predecessors derives the parents from
+ * the depths this call delivers. */
 int grx_bfs(grx_context_t ctx, grx_graph_t g, int32_t source, int32_t* d_distances,
             int32_t* d_predecessors, const grx_options* opt, grx_stats* stats);
 /* sssp::run(G, source, distances, predecessors, context)  algorithms/sssp.hxx:155-185.
- * d_distances: float[V] out (FLT_MAX = unreached).
+ * d_distances: float[V] out (FLT_MAX = unreached).  d_predecessors: as for grx_bfs, may be NULL,
+ * never written: grx_sssp_predecessors derives the tree from the distances this call delivers.
  * On a graph KNOWN to be its own transpose with equal weights in both directions (grx_graph_rmat
  * with symmetrize, grx_graph_from_mtx on a symmetric file; no check is ever run for this) the wide
  * rounds that follow a near / far selection are pulled over a copy of the rows sorted by ascending
@@ -903,6 +905,63 @@ int grx_spmv(grx_context_t ctx, grx_graph_t g, int32_t transpose, const float* d
  * long row and 12 per segment at most), twice with in-edges attached. */
 int grx_hits(grx_context_t ctx, grx_graph_t g, float tol, float* d_hub, float* d_authority,
              int32_t* h_iterations, float* h_residual, const grx_options* opt, grx_stats* stats);
+/* Shortest-path trees: the predecessors that finished labels imply, a count of the entries that
+ * contradict the labels, and (SSSP) hop counts along the tree.  The reference left predecessors as a
+ * "@todo" (bfs.hxx:28) and grx_bfs / grx_sssp ignore the argument; these two calls derive the tree in
+ * one pass over the entries from what those calls delivered.  The labels (d_depths: device int32[V],
+ * INT32_MAX = unreached; d_distances: device float[V], FLT_MAX = unreached) are in the caller's
+ * numbering and are plain input: any array is accepted, and the results are a function of the CSR
+ * arrays, the labels and the source alone.
+ * For every row entry (u, v, w) whose label[u] is not the unreached value:
+ *   BFS   the entry QUALIFIES when depth[u] + 1 == depth[v] and VIOLATES when depth[u] + 1 < depth[v]
+ *         (in 64-bit integers);
+ *   SSSP  with c = dist[u] + w as ONE float32 add, it qualifies when c == dist[v] and dist[u] < dist[v],
+ *         and violates when c < dist[v].  A NaN makes every comparison false: it qualifies nothing and
+ *         violates nothing.
+ * The add is the one every relaxation of grx_sssp performs, pushed or pulled, so at its fixed point
+ * every reached vertex but the source has a qualifying entry bit for bit.
+ * d_predecessors (device int32[V] out): for a reached v != source the SMALLEST u with a qualifying
+ * entry into v; every qualifying entry lowers the label strictly, so chains of predecessors never
+ * cycle, whatever the input.  d_predecessors[source] = source (the Graph500 convention); -1 for an
+ * unreached v; -2 for an ORPHAN, a reached vertex other than the source without a qualifying entry.
+ * On the labels of a finished search an orphan exists only where a zero weight, or a weight absorbed
+ * by rounding, leaves dist[v] == dist[u]; on integer weights >= 1 with distances below 2^24, and on
+ * any BFS result, there is none.
+ * h_orphans (HOST int64): the orphans.  h_violations (HOST int64): the violating entries, 0 exactly
+ * when the labels are a fixed point of relaxation; a search cut off by max_iterations shows here.
+ * d_hops (SSSP only, device int32[V] out, may be NULL): the predecessor steps from v to the source, 0
+ * at the source, -1 for a vertex that is unreached, an orphan, or whose chain ends in an orphan.  (For
+ * BFS it would equal the depth.)
+ * d_predecessors may be NULL when another output is asked for (the call then works on an array of its
+ * own); every output NULL is GRX_ERR_INVALID_ARGUMENT.  So are, all found before anything is
+ * launched: a NULL ctx, g or labels; n_rows != n_cols; opt->max_iterations != 0; source out of range;
+ * label[source] != 0 (read by a 4-byte copy on the context's stream).  V == 0 is GRX_OK with both
+ * counts 0 and nothing written.  opt may be NULL; only collect_kernel_time is read.
+ * Which entries: the call runs on the caller's CSR as given.  It neither builds nor uses a hot-first
+ * copy, starts no symmetry verification, leaves nothing on the handle and releases its workspace on
+ * return (at most 4 bytes per vertex without d_predecessors, 16 per vertex with d_hops, 24 bytes per
+ * GRX_TREE_SEGMENT entries).  Two forms of the pass give the same outputs.  PULL walks in-rows with a
+ * group of 16 lanes per vertex and no atomics on rows of at most GRX_TREE_SEGMENT entries (default
+ * 512, minimum 64; an environment variable read per call, a test hook); it runs when in-edges are
+ * attached (their values are the entries' weights), or the handle's symmetry verdict is ALREADY
+ * "symmetric" (for SSSP: and its builder vouched for equal weights in both directions, as grx_sssp
+ * asks before it pulls).  PUSH walks out-rows and lowers d_predecessors[v] by a 32-bit atomicMin; it
+ * runs in every other case, and whenever GRX_TREE_PULL=0.  Only integer minima, integer sums and
+ * plain stores are used: the same call returns bit-identical outputs, in either form.
+ * d_hops is pointer doubling on 8-byte {ancestor, steps} pairs in two buffers that take turns, four
+ * rounds enqueued per host hand-off (a round past the last changing one copies its input); more than
+ * 32 rounds is GRX_ERR_RUNTIME (chains shorter than 2^31 need fewer).
+ * stats may be NULL; set: elapsed_ms, advance_kernel_ms (with collect_kernel_time), advance_launches
+ * (kernel launches), vertices_reached (the labels that are not the unreached value), edges_traversed
+ * = edges_expanded = nnz, pull_iterations (1 when the pull form ran, else 0), iterations (0 without
+ * d_hops, else ceil(log2(L)), L the largest number of predecessor steps from any vertex to the end
+ * of its chain, the source or an orphan; 0 for L <= 1); everything else 0. */
+int grx_bfs_predecessors(grx_context_t ctx, grx_graph_t g, int32_t source, const int32_t* d_depths,
+                         int32_t* d_predecessors, int64_t* h_orphans, int64_t* h_violations,
+                         const grx_options* opt, grx_stats* stats);
+int grx_sssp_predecessors(grx_context_t ctx, grx_graph_t g, int32_t source, const float* d_distances,
+                          int32_t* d_predecessors, int32_t* d_hops, int64_t* h_orphans,
+                          int64_t* h_violations, const grx_options* opt, grx_stats* stats);
 /* Random walks: first-order uniform and weighted walks and node2vec (second-order, by rejection),
  * the corpus of DeepWalk / node2vec and of random-walk samplers.  No reference counterpart.  Every
  * draw comes from a counter-based generator, so the answer is a function of the CSR and the arguments
