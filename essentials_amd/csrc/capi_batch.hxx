@@ -2,23 +2,33 @@
  * @file capi_batch.hxx
  * @brief Host scaffold of the calls that are batches of their own kernels rather than operator
  * pipelines (grx_tc, grx_kcore, grx_cc, grx_mst, grx_color; grx_bc takes the grid and the clock):
- * grid sizing, the call's clock, the hand-off that ends a batch, the symmetric-CSR gate,
- * and what the generation-queue calls (grx_kcore, grx_color) share.  Not installed.
+ * grid sizing, the call's clock, the hand-off that ends a batch, the symmetric-CSR gate, what the
+ * generation-queue calls (grx_kcore, grx_color) share, and the rows and the long-row plan of the
+ * lane-group sweep (grx_spmv, grx_hits, the predecessors calls; grx_ppr takes the rows).  Not installed.
  */
 #pragma once
 
 #include "capi_internal.hxx"
 
 #include <gunrock/hip/kernels/generation_queue.hxx>
+#include <gunrock/hip/kernels/group_rows.hxx>
 
 #include <cstdlib>
 #include <cstring>
 
 namespace essentials_amd {
 
+namespace k = gunrock::hip::kernels;  // a caller's own alias of this name names the same
+
 /// Workgroups for `items` at `per_block` each: at least one, at most eight per CU.
 inline unsigned grid_for(std::size_t items, std::size_t per_block, gcuda::standard_context_t& ctx) {
   return hip::grid_for(items, per_block, (unsigned)ctx.compute_units() * 8u);
+}
+
+/// grid_for made odd: the rows a workgroup walks are a grid stride apart, and with a power of two for
+/// a stride they would share their low bits -- on R-MAT, their weight class.
+inline unsigned odd_grid_for(std::size_t rows, std::size_t per_block, gcuda::standard_context_t& ctx) {
+  return grid_for(rows, per_block, ctx) | 1u;
 }
 
 /// The two clocks of a call: the whole call (grx_stats::elapsed_ms) and, when `timed`
@@ -90,7 +100,6 @@ inline int require_symmetric(grx_context_s* ctx, grx_graph_s* g, const char* cal
 template <typename wide_t, typename big_t, typename narrow_t>
 int32_t run_generations(gcuda::standard_context_t& sc, call_clock_t& clock, unsigned long long*& m, int32_t block,
                         bool has_big, int32_t& launches, wide_t&& wide, big_t&& big, narrow_t&& narrow) {
-  namespace k = gunrock::hip::kernels;
   const int32_t most = (int32_t)sc.compute_units() * 8;
   int32_t generations = 0;
   for (; m[k::GQ_TAIL] > m[k::GQ_HEAD]; ++generations) {
@@ -122,5 +131,51 @@ inline void queue_call_stats(grx_stats* stats, call_clock_t& clock, int32_t iter
   stats->edges_traversed = traversed;
   stats->edges_expanded = (int64_t)expanded;
 }
+
+inline k::csr_rows_t out_rows(const grx_graph_s* g) { return {g->d_ap, g->d_aj, g->d_ax}; }
+
+/// The attached in-edge arrays, else the CSR itself: the caller knows that its rows are its in-rows.
+inline k::csr_rows_t in_rows(const grx_graph_s* g) {
+  if (!g->in_edges)
+    return out_rows(g);
+  return {g->in_edges->offsets.data(), g->in_edges->indices.data(), g->in_edges->values.data()};
+}
+
+/// One set of rows of the lane-group sweep (hip/kernels/group_rows.hxx) with the list of its long ones.
+struct row_plan_t {
+  k::csr_rows_t rows{};
+  k::group_plan_t plan{};
+  int32_t n = 0, segment = 0;
+  bool any_long = false;  // nnz > segment: otherwise no row can be long and nothing is planned
+  hip::device_array_t<int32_t> counts;
+  hip::device_array_t<int2> long_rows, items;
+
+  /// Enqueue the plan; returns the launches.
+  int build(const k::csr_rows_t& r, int32_t n_rows, int64_t nnz, int32_t seg, gcuda::standard_context_t& sc) {
+    rows = r;
+    n = n_rows;
+    segment = seg;
+    any_long = nnz > (int64_t)seg;
+    if (!any_long)
+      return 0;
+    // a long row has more than `segment` entries, and ceil(d / segment) < d / segment + 1 per row
+    const std::size_t most_rows = (std::size_t)(nnz / seg) + 1, most_items = 2 * most_rows;
+    counts = hip::device_array_t<int32_t>(2);
+    long_rows = hip::device_array_t<int2>(most_rows);
+    items = hip::device_array_t<int2>(most_items);
+    plan = k::group_plan_t{counts.data(), long_rows.data(), items.data(),
+                           (int32_t)std::min<std::size_t>(most_rows, INT32_MAX),
+                           (int32_t)std::min<std::size_t>(most_items, INT32_MAX)};
+    GRX_HIP_CHECK(hipMemsetAsync(counts.data(), 0, 2 * sizeof(int32_t), sc.stream()));
+    k::group_plan_kernel<><<<grid_for((std::size_t)n, k::GROUP_BLOCK, sc), k::GROUP_BLOCK, 0, sc.stream()>>>(
+        rows, n, segment, plan);
+    return 1;
+  }
+
+  /// The grids: a lane group per row, a lane group per item, a thread per long row.
+  unsigned per_row(gcuda::standard_context_t& sc) const { return odd_grid_for(n, k::GROUP_ROWS, sc); }
+  unsigned per_item(gcuda::standard_context_t& sc) const { return grid_for(plan.most_items, k::GROUP_ROWS, sc); }
+  unsigned per_long_row(gcuda::standard_context_t& sc) const { return grid_for(plan.most_rows, k::GROUP_BLOCK, sc); }
+};
 
 }  // namespace essentials_amd

@@ -88,9 +88,7 @@ extern "C" int grx_ppr(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds,
     unsigned long long nonzero_total = 0;
     {
       const std::size_t nv = (std::size_t)n, nnz = (std::size_t)g->nnz;
-      const k::ppr_rows_t in = g->in_edges ? k::ppr_rows_t{g->in_edges->offsets.data(), g->in_edges->indices.data(),
-                                                           g->in_edges->values.data()}
-                                           : k::ppr_rows_t{g->d_ap, g->d_aj, g->d_ax};
+      const k::csr_rows_t in = in_rows(g);
       // once per call: scale, the dangling list, the long in-rows and their items
       const std::size_t most_long = nnz / (std::size_t)segment + 1;  // a long row has more than `segment` entries
       const std::size_t most_items = 2 * most_long;                  // ceil(d / segment) < d / segment + 1 per row
@@ -163,9 +161,7 @@ extern "C" int grx_ppr(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds,
             // a column that contracts stops long before this; NaN weights never do
             error::throw_if_exception(t > (1 << 20), "grx_ppr: no column below tol after 2^20 iterations");
             const k::ppr_state_t st{scale.data(), p, give, next, seeds, frozen, alpha, ctr};
-            // an odd grid: the rows of a workgroup are a stride apart, and with a power of two for a
-            // stride they would share their low bits -- on R-MAT, their weight class
-            k::ppr_gather_kernel<W><<<grid_for(nv, rows, sc) | 1u, k::PPR_BLOCK, 0, s>>>(in, st, n, segment);
+            k::ppr_gather_kernel<W><<<odd_grid_for(nv, rows, sc), k::PPR_BLOCK, 0, s>>>(in, st, n, segment);
             ++launches;
             if (n_long) {
               k::ppr_segment_kernel<W><<<grid_for((std::size_t)n_items, rows, sc), k::PPR_BLOCK, 0, s>>>(

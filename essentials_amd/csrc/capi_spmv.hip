@@ -19,40 +19,19 @@ namespace {
 
 /// The entries one lane group sums (a test hook, read per call).
 int32_t segment_entries() {
-  return (int32_t)env_or("GRX_SPMV_SEGMENT", k::SPMV_SEGMENT, k::SPMV_SEGMENT_MIN, INT32_MAX);
+  return (int32_t)env_or("GRX_SPMV_SEGMENT", k::GROUP_SEGMENT, k::GROUP_SEGMENT_MIN, INT32_MAX);
 }
 
-/// One set of rows with the list of its long ones and the room for their partial sums.
-struct product_rows_t {
-  k::spmv_rows_t rows{};
-  k::spmv_plan_t plan{};
-  int32_t n = 0, segment = 0;
-  bool any_long = false;  // nnz > segment: otherwise no row can be long and nothing is planned
-  hip::device_array_t<int32_t> counts;
-  hip::device_array_t<int2> long_rows, items;
+/// The rows of a product, the list of its long ones and the room for their partial sums.
+struct product_rows_t : row_plan_t {
   hip::device_array_t<float> partial;
 
   /// Enqueue the plan; returns the launches.
-  int build(const k::spmv_rows_t& r, int32_t n_rows, int64_t nnz, int32_t seg, gcuda::standard_context_t& sc) {
-    rows = r;
-    n = n_rows;
-    segment = seg;
-    any_long = nnz > (int64_t)seg;
-    if (!any_long)
-      return 0;
-    // a long row has more than `segment` entries, and ceil(d / segment) < d / segment + 1 per row
-    const std::size_t most_rows = (std::size_t)(nnz / seg) + 1, most_items = 2 * most_rows;
-    counts = hip::device_array_t<int32_t>(2);
-    long_rows = hip::device_array_t<int2>(most_rows);
-    items = hip::device_array_t<int2>(most_items);
-    partial = hip::device_array_t<float>(most_items);
-    plan = k::spmv_plan_t{counts.data(), long_rows.data(), items.data(),
-                          (int32_t)std::min<std::size_t>(most_rows, INT32_MAX),
-                          (int32_t)std::min<std::size_t>(most_items, INT32_MAX)};
-    GRX_HIP_CHECK(hipMemsetAsync(counts.data(), 0, 2 * sizeof(int32_t), sc.stream()));
-    k::spmv_plan_kernel<><<<grid_for((std::size_t)n, k::SPMV_BLOCK, sc), k::SPMV_BLOCK, 0, sc.stream()>>>(
-        rows, n, segment, plan);
-    return 1;
+  int build(const k::csr_rows_t& r, int32_t n_rows, int64_t nnz, int32_t seg, gcuda::standard_context_t& sc) {
+    const int launches = row_plan_t::build(r, n_rows, nnz, seg, sc);
+    if (any_long)
+      partial = hip::device_array_t<float>((std::size_t)plan.most_items);
+    return launches;
   }
 
   /// Enqueue y = rows * (x scaled by the word at scale_bits); returns the launches.
@@ -60,26 +39,17 @@ struct product_rows_t {
   int product(const float* x, const unsigned* scale_bits, float* y, unsigned* max_bits,
               gcuda::standard_context_t& sc) const {
     const hipStream_t s = sc.stream();
-    // an odd grid: the rows of a workgroup are a stride apart, and with a power of two for a stride
-    // they would share their low bits -- on R-MAT, their weight class (capi_ppr.hip)
-    k::spmv_gather_kernel<SCALED, TRACK><<<grid_for((std::size_t)n, k::SPMV_ROWS, sc) | 1u, k::SPMV_BLOCK, 0, s>>>(
-        rows, x, scale_bits, n, segment, y, max_bits);
+    k::spmv_gather_kernel<SCALED, TRACK><<<per_row(sc), k::GROUP_BLOCK, 0, s>>>(rows, x, scale_bits, n, segment, y,
+                                                                              max_bits);
     if (!any_long)
       return 1;
-    k::spmv_segment_kernel<SCALED><<<grid_for((std::size_t)plan.most_items, k::SPMV_ROWS, sc), k::SPMV_BLOCK, 0, s>>>(
-        rows, x, scale_bits, plan, segment, partial.data());
-    k::spmv_combine_kernel<TRACK><<<grid_for((std::size_t)plan.most_rows, k::SPMV_BLOCK, sc), k::SPMV_BLOCK, 0, s>>>(
-        rows, plan, segment, partial.data(), y, max_bits);
+    k::spmv_segment_kernel<SCALED><<<per_item(sc), k::GROUP_BLOCK, 0, s>>>(rows, x, scale_bits, plan, segment,
+                                                                         partial.data());
+    k::spmv_combine_kernel<TRACK><<<per_long_row(sc), k::GROUP_BLOCK, 0, s>>>(rows, plan, segment, partial.data(), y,
+                                                                            max_bits);
     return 3;
   }
 };
-
-k::spmv_rows_t out_rows(const grx_graph_s* g) { return k::spmv_rows_t{g->d_ap, g->d_aj, g->d_ax}; }
-k::spmv_rows_t in_rows(const grx_graph_s* g) {
-  return g->in_edges ? k::spmv_rows_t{g->in_edges->offsets.data(), g->in_edges->indices.data(),
-                                      g->in_edges->values.data()}
-                     : out_rows(g);
-}
 
 bool overlap(const float* a, std::size_t na, const float* b, std::size_t nb) {
   const std::uintptr_t a0 = (std::uintptr_t)a, b0 = (std::uintptr_t)b;
@@ -186,7 +156,7 @@ extern "C" int grx_hits(grx_context_t ctx, grx_graph_t g, float tol, float* d_hu
       if (g->in_edges)
         launches += in_own.build(in_rows(g), n, g->nnz, segment, sc);
       const product_rows_t& in = g->in_edges ? in_own : out;
-      k::hits_begin_kernel<><<<grid_for(nv, k::SPMV_BLOCK, sc), k::SPMV_BLOCK, 0, s>>>(z[0], n, ctl);
+      k::hits_begin_kernel<><<<grid_for(nv, k::GROUP_BLOCK, sc), k::GROUP_BLOCK, 0, s>>>(z[0], n, ctl);
       ++launches;
 
       int32_t t = 0;
@@ -199,7 +169,7 @@ extern "C" int grx_hits(grx_context_t ctx, grx_graph_t g, float tol, float* d_hu
         launches += in.product<true, true>(z[old], &ctl->h_max[old], y, &ctl->a_max, sc);
         launches += out.product<true, true>(y, &ctl->a_max, z[now], &ctl->h_max[now], sc);
         if (by_tol || last) {  // otherwise nobody reads this iteration's residual
-          k::hits_residual_kernel<><<<grid_for(nv, k::SPMV_BLOCK, sc), k::SPMV_BLOCK, 0, s>>>(z[0], z[1], now, n, ctl);
+          k::hits_residual_kernel<><<<grid_for(nv, k::GROUP_BLOCK, sc), k::GROUP_BLOCK, 0, s>>>(z[0], z[1], now, n, ctl);
           ++launches;
         }
         ++launches;
@@ -219,7 +189,7 @@ extern "C" int grx_hits(grx_context_t ctx, grx_graph_t g, float tol, float* d_hu
         if (diff < tol || last)
           break;
       }
-      k::hits_deliver_kernel<><<<grid_for(nv, k::SPMV_BLOCK, sc), k::SPMV_BLOCK, 0, s>>>(z[t & 1], y, t & 1, n, d_hub,
+      k::hits_deliver_kernel<><<<grid_for(nv, k::GROUP_BLOCK, sc), k::GROUP_BLOCK, 0, s>>>(z[t & 1], y, t & 1, n, d_hub,
                                                                                         d_authority, ctl);
       GRX_HIP_CHECK(hipGetLastError());
       clock.end_batch();

@@ -65,12 +65,7 @@ int tree_call(const char* call, grx_context_t ctx, grx_graph_t g, int32_t source
     // pull over in-rows whenever somebody has already said what they are
     const bool own_rows_are_in_rows = g->symmetry == grx_graph_s::symmetric && (!weighted || g->weight_symmetric);
     const bool pull = env_flag("GRX_TREE_PULL", true) && (g->in_edges || own_rows_are_in_rows);
-    const k::spmv_rows_t rows =
-        pull && g->in_edges
-            ? k::spmv_rows_t{g->in_edges->offsets.data(), g->in_edges->indices.data(), g->in_edges->values.data()}
-            : k::spmv_rows_t{g->d_ap, g->d_aj, g->d_ax};
-    const int32_t segment = (int32_t)env_or("GRX_TREE_SEGMENT", k::TREE_SEGMENT, k::TREE_SEGMENT_MIN, INT32_MAX);
-    const bool any_long = g->nnz > (int64_t)segment;  // otherwise no row can be long and nothing is planned
+    const int32_t segment = (int32_t)env_or("GRX_TREE_SEGMENT", k::GROUP_SEGMENT, k::GROUP_SEGMENT_MIN, INT32_MAX);
     const std::size_t nv = (std::size_t)n;
 
     call_clock_t clock(s, timed);
@@ -79,8 +74,9 @@ int tree_call(const char* call, grx_context_t ctx, grx_graph_t g, int32_t source
     unsigned long long h_counts[k::TREE_WORDS] = {};
     {
       hip::device_array_t<unsigned long long> counts(k::TREE_WORDS);
-      hip::device_array_t<int32_t> own_pred, plan_counts;
-      hip::device_array_t<int2> long_rows, items, pairs;
+      hip::device_array_t<int32_t> own_pred;
+      hip::device_array_t<int2> pairs;
+      row_plan_t walk;
       int32_t* pred = out.d_predecessors;
       if (!pred) {
         own_pred = hip::device_array_t<int32_t>(nv);
@@ -88,59 +84,43 @@ int tree_call(const char* call, grx_context_t ctx, grx_graph_t g, int32_t source
       }
       clock.begin_batch();
       GRX_HIP_CHECK(hipMemsetAsync(counts.data(), 0, k::TREE_WORDS * sizeof(unsigned long long), s));
-      k::spmv_plan_t plan{};
-      if (any_long) {
-        // a long row has more than `segment` entries, and ceil(d / segment) < d / segment + 1 per row
-        const std::size_t most_rows = (std::size_t)(g->nnz / segment) + 1, most_items = 2 * most_rows;
-        plan_counts = hip::device_array_t<int32_t>(2);
-        long_rows = hip::device_array_t<int2>(most_rows);
-        items = hip::device_array_t<int2>(most_items);
-        plan = k::spmv_plan_t{plan_counts.data(), long_rows.data(), items.data(),
-                              (int32_t)std::min<std::size_t>(most_rows, INT32_MAX),
-                              (int32_t)std::min<std::size_t>(most_items, INT32_MAX)};
-        GRX_HIP_CHECK(hipMemsetAsync(plan_counts.data(), 0, 2 * sizeof(int32_t), s));
-        k::spmv_plan_kernel<><<<grid_for(nv, k::SPMV_BLOCK, sc), k::SPMV_BLOCK, 0, s>>>(rows, n, segment, plan);
-        ++launches;
-      }
-      const unsigned per_vertex = grid_for(nv, k::TREE_BLOCK, sc);
-      // an odd grid: the rows of a workgroup are a stride apart (capi_spmv.hip)
-      const unsigned per_row = grid_for(nv, k::TREE_ROWS, sc) | 1u;
-      const unsigned per_item = grid_for((std::size_t)plan.most_items, k::TREE_ROWS, sc);
+      launches += walk.build(pull ? in_rows(g) : out_rows(g), n, g->nnz, segment, sc);
+      const unsigned per_vertex = grid_for(nv, k::GROUP_BLOCK, sc), per_row = walk.per_row(sc);
       if (pull) {
-        k::tree_rows_kernel<label_t, false><<<per_row, k::TREE_BLOCK, 0, s>>>(rows, d_labels, n, segment, source, pred,
-                                                                             counts.data());
+        k::tree_rows_kernel<label_t, false><<<per_row, k::GROUP_BLOCK, 0, s>>>(walk.rows, d_labels, n, segment, source,
+                                                                              pred, counts.data());
         ++launches;
-        if (any_long) {
-          k::tree_segment_kernel<label_t, false><<<per_item, k::TREE_BLOCK, 0, s>>>(rows, d_labels, plan, segment, pred,
-                                                                                   counts.data());
-          k::tree_fixup_kernel<label_t><<<grid_for((std::size_t)plan.most_rows, k::TREE_BLOCK, sc), k::TREE_BLOCK, 0, s>>>(
-              d_labels, plan, source, pred, counts.data());
+        if (walk.any_long) {
+          k::tree_segment_kernel<label_t, false><<<walk.per_item(sc), k::GROUP_BLOCK, 0, s>>>(
+              walk.rows, d_labels, walk.plan, segment, pred, counts.data());
+          k::tree_fixup_kernel<label_t><<<walk.per_long_row(sc), k::GROUP_BLOCK, 0, s>>>(d_labels, walk.plan, source, pred,
+                                                                                      counts.data());
           launches += 2;
         }
       } else {
-        k::tree_fill_kernel<><<<per_vertex, k::TREE_BLOCK, 0, s>>>(pred, n);
-        k::tree_rows_kernel<label_t, true><<<per_row, k::TREE_BLOCK, 0, s>>>(rows, d_labels, n, segment, source, pred,
-                                                                            counts.data());
+        k::tree_fill_kernel<><<<per_vertex, k::GROUP_BLOCK, 0, s>>>(pred, n);
+        k::tree_rows_kernel<label_t, true><<<per_row, k::GROUP_BLOCK, 0, s>>>(walk.rows, d_labels, n, segment, source,
+                                                                             pred, counts.data());
         launches += 2;
-        if (any_long) {
-          k::tree_segment_kernel<label_t, true><<<per_item, k::TREE_BLOCK, 0, s>>>(rows, d_labels, plan, segment, pred,
-                                                                                  counts.data());
+        if (walk.any_long) {
+          k::tree_segment_kernel<label_t, true><<<walk.per_item(sc), k::GROUP_BLOCK, 0, s>>>(
+              walk.rows, d_labels, walk.plan, segment, pred, counts.data());
           ++launches;
         }
-        k::tree_finalise_kernel<label_t><<<per_vertex, k::TREE_BLOCK, 0, s>>>(d_labels, n, source, pred, counts.data());
+        k::tree_finalise_kernel<label_t><<<per_vertex, k::GROUP_BLOCK, 0, s>>>(d_labels, n, source, pred, counts.data());
         ++launches;
       }
       if (out.d_hops) {
         pairs = hip::device_array_t<int2>(2 * nv);
         int2* pair[2] = {pairs.data(), pairs.data() + nv};
-        k::tree_hops_begin_kernel<><<<per_vertex, k::TREE_BLOCK, 0, s>>>(pred, n, pair[0]);
+        k::tree_hops_begin_kernel<><<<per_vertex, k::GROUP_BLOCK, 0, s>>>(pred, n, pair[0]);
         ++launches;
         unsigned long long* changed = counts.data() + k::TREE_CHANGED;
         for (bool settled = false; !settled;) {
           // a chain of fewer than 2^31 steps is at its end after 31 rounds, and the 32nd changes nothing
           error::throw_if_exception(rounds >= 32, name + ": the chains are not at their ends after 32 rounds");
           for (int j = 0; j < k::TREE_ROUNDS_AHEAD; ++j)  // a round past the last changing one copies
-            k::tree_hops_round_kernel<><<<per_vertex, k::TREE_BLOCK, 0, s>>>(pair[(rounds + j) & 1],
+            k::tree_hops_round_kernel<><<<per_vertex, k::GROUP_BLOCK, 0, s>>>(pair[(rounds + j) & 1],
                                                                            pair[~(rounds + j) & 1], n, changed + j);
           launches += k::TREE_ROUNDS_AHEAD + 1;
           unsigned long long* m = hand_off(sc, clock, [&](unsigned long long* mirror, int slot, unsigned long long seq) {
@@ -153,7 +133,7 @@ int tree_call(const char* call, grx_context_t ctx, grx_graph_t g, int32_t source
           rounds += k::TREE_ROUNDS_AHEAD;
           clock.begin_batch();
         }
-        k::tree_hops_end_kernel<><<<per_vertex, k::TREE_BLOCK, 0, s>>>(pair[rounds & 1], n, source, out.d_hops);
+        k::tree_hops_end_kernel<><<<per_vertex, k::GROUP_BLOCK, 0, s>>>(pair[rounds & 1], n, source, out.d_hops);
         ++launches;
       }
       GRX_HIP_CHECK(hipGetLastError());

@@ -38,7 +38,7 @@
  */
 #pragma once
 
-#include <gunrock/hip/kernels/row_walk.hxx>
+#include <gunrock/hip/kernels/group_rows.hxx>  // csr_rows_t, here the in-entries
 
 namespace gunrock {
 namespace hip {
@@ -66,13 +66,6 @@ enum { PM_FROZEN = 0, PM_WORDS };
 /// The seeds of a batch, by value; -1 in a column the batch does not use.
 struct ppr_seeds_t {
   int32_t v[PPR_BATCH];
-};
-
-/// The in-entries: the attached in-edge arrays, or the CSR itself when it is symmetric.
-struct ppr_rows_t {
-  const int32_t* ap;
-  const int32_t* aj;
-  const float* ax;
 };
 
 /// What the kernels that finish a vertex share.
@@ -103,7 +96,7 @@ __device__ __forceinline__ void ppr_place(int& group, int& column) {
 
 /// Sum over entries [lo, hi) of give[source][c] * weight, sequentially in entry order from 0.
 template <int L>
-__device__ __forceinline__ float ppr_row_sum(const ppr_rows_t& in, const float* give, int32_t lo, int32_t hi, int c) {
+__device__ __forceinline__ float ppr_row_sum(const csr_rows_t& in, const float* give, int32_t lo, int32_t hi, int c) {
   float acc = 0.0f;
   int32_t e = lo;
   if (e + PPR_FLIGHT <= hi) {
@@ -199,7 +192,7 @@ __device__ __forceinline__ void ppr_flush(float worst, int c, unsigned* s_diff, 
 /// and the two flags the lists are built from.  A wavefront per row: lane l sums entries l, l + 64,
 /// ... in order, the 64 sums meet in a butterfly -- an order fixed by the row alone.
 __global__ void __launch_bounds__(PPR_BLOCK)
-    ppr_scale_kernel(const int32_t* ap, const float* ax, ppr_rows_t in, float alpha, int32_t n, int32_t segment,
+    ppr_scale_kernel(const int32_t* ap, const float* ax, csr_rows_t in, float alpha, int32_t n, int32_t segment,
                      float* scale, unsigned char* is_dangling, unsigned char* is_long) {
   const int lane = lane_id();
   const int64_t waves = (int64_t)gridDim.x * (PPR_BLOCK / wave_size);
@@ -220,7 +213,7 @@ __global__ void __launch_bounds__(PPR_BLOCK)
 /// Once per call, one workgroup: first[r] = the first item of long row r (first[rows] = the items),
 /// and the items {vertex, segment} themselves, row after row.
 __global__ void __launch_bounds__(PPR_BLOCK)
-    ppr_items_kernel(ppr_rows_t in, const int32_t* long_rows, const int32_t* n_long, int32_t segment, int32_t* first,
+    ppr_items_kernel(csr_rows_t in, const int32_t* long_rows, const int32_t* n_long, int32_t segment, int32_t* first,
                      int2* items, int32_t capacity) {
   __shared__ int32_t s_wave[PPR_BLOCK / wave_size + 1];
   const int32_t rows = *n_long;
@@ -265,7 +258,7 @@ __global__ void ppr_seed_kernel(ppr_seeds_t seeds, int width, const float* scale
 
 /// The in-rows of at most `segment` entries, a lane group each.
 template <int L>
-__global__ void __launch_bounds__(PPR_BLOCK) ppr_gather_kernel(ppr_rows_t in, ppr_state_t s, int32_t n, int32_t segment) {
+__global__ void __launch_bounds__(PPR_BLOCK) ppr_gather_kernel(csr_rows_t in, ppr_state_t s, int32_t n, int32_t segment) {
   __shared__ unsigned s_diff[PPR_BATCH];
   if (threadIdx.x < PPR_BATCH)
     s_diff[threadIdx.x] = 0;
@@ -292,7 +285,7 @@ __global__ void __launch_bounds__(PPR_BLOCK) ppr_gather_kernel(ppr_rows_t in, pp
 /// The items of the long in-rows, a lane group each: partial[item] = the sum over its segment.
 template <int L>
 __global__ void __launch_bounds__(PPR_BLOCK)
-    ppr_segment_kernel(ppr_rows_t in, const float* give, const int2* items, int32_t n_items, int32_t segment,
+    ppr_segment_kernel(csr_rows_t in, const float* give, const int2* items, int32_t n_items, int32_t segment,
                        float* partial) {
   int group, c;
   ppr_place<L>(group, c);

@@ -3,15 +3,11 @@
  * @brief Sparse matrix-vector products whose every row sum has a fixed order (grx_spmv), and the
  * HITS iteration built from two of them (grx_hits).
  *
- * A 16-lane group sums one row: lane l adds entries l, l + 16, ... in order, one fused multiply-add
- * each, and the 16 sums meet in a butterfly (xor 8, 4, 2, 1).  A wavefront holds four groups, a
- * workgroup sixteen; R-MAT rows are about 16 entries, so a group reads one 64-byte segment of column
- * ids per step.  A row of more than `segment` entries is cut once per call (spmv_plan_kernel) into
- * items {row, k} of `segment` entries; a group sums one item the same way into partial[] and one
- * thread per long row adds its partials in segment order (spmv_combine_kernel).  The order of a sum
- * depends on the row's layout and `segment` alone: never on the grid, the CU count or arrival order.
- * The plan appends rows and items with integer atomics, so where an item sits in the list varies
- * from run to run; which entries it covers and the order they are added in do not.
+ * A 16-lane group sums one row by the sweep of group_rows.hxx: lane l adds entries l, l + 16, ... in
+ * order, one fused multiply-add each, and the 16 sums meet in the butterfly.  A lane group sums one
+ * item of a long row the same way into partial[] and one thread per long row adds its partials in
+ * segment order (spmv_combine_kernel).  The order of a sum depends on the row's layout and `segment`
+ * alone: never on the grid, the CU count or arrival order.
  *
  * The operand may carry a scale: with SCALED the value read for column c is x[c] * r, r the rounded
  * reciprocal of a maximum an EARLIER kernel left in a device word (0 when that maximum is 0).  With
@@ -36,33 +32,11 @@
  */
 #pragma once
 
-#include <gunrock/hip/kernels/row_walk.hxx>
+#include <gunrock/hip/kernels/group_rows.hxx>
 
 namespace gunrock {
 namespace hip {
 namespace kernels {
-
-constexpr int SPMV_BLOCK = 256;
-constexpr int SPMV_GROUP = 16;                        // lanes that share a row
-constexpr int SPMV_ROWS = SPMV_BLOCK / SPMV_GROUP;    // rows a workgroup sums side by side
-constexpr int SPMV_SEGMENT = 512;                     // default: row entries one lane group sums
-constexpr int SPMV_SEGMENT_MIN = 64;
-constexpr int SPMV_FLIGHT = 4;                        // entries in flight per lane
-
-/// The rows a product walks: the CSR, or the attached in-edge arrays.
-struct spmv_rows_t {
-  const int32_t* ap;
-  const int32_t* aj;
-  const float* ax;
-};
-
-/// The long rows of one spmv_rows_t: rows[j] = {row, its first item}, items[i] = {row, segment}.
-struct spmv_plan_t {
-  int32_t* counts;  // [0] long rows, [1] items; zero before spmv_plan_kernel
-  int2* rows;
-  int2* items;
-  int32_t most_rows, most_items;  // what the arrays hold (sized by the host from nnz)
-};
 
 /// Device words of a grx_hits call.
 struct hits_ctl_t {
@@ -87,36 +61,13 @@ __device__ __forceinline__ float spmv_reciprocal(const unsigned* max_bits) {
 /// The sum over entries [lo, hi) as the header says; valid in all 16 lanes of the group.  Every lane of
 /// the wavefront calls it (an empty range gives 0).
 template <bool SCALED>
-__device__ __forceinline__ float spmv_group_sum(const spmv_rows_t& rows, const float* x, float r, int32_t lo,
+__device__ __forceinline__ float spmv_group_sum(const csr_rows_t& rows, const float* x, float r, int32_t lo,
                                                 int32_t hi, int lane) {
   float acc = 0.0f;
-  for (int32_t e = lo + lane; e < hi; e += SPMV_GROUP * SPMV_FLIGHT) {
-    int32_t c[SPMV_FLIGHT];
-    float w[SPMV_FLIGHT], v[SPMV_FLIGHT];
-#pragma unroll
-    for (int k = 0; k < SPMV_FLIGHT; ++k) {  // a slot past the end reads nothing
-      c[k] = 0;
-      w[k] = 0.0f;
-      if (e + k * SPMV_GROUP < hi) {
-        c[k] = rows.aj[e + k * SPMV_GROUP];
-        w[k] = rows.ax[e + k * SPMV_GROUP];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < SPMV_FLIGHT; ++k) {
-      v[k] = 0.0f;
-      if (e + k * SPMV_GROUP < hi)
-        v[k] = x[c[k]];
-    }
-#pragma unroll
-    for (int k = 0; k < SPMV_FLIGHT; ++k)
-      if (e + k * SPMV_GROUP < hi)
-        acc = __fmaf_rn(SCALED ? __fmul_rn(v[k], r) : v[k], w[k], acc);
-  }
-#pragma unroll
-  for (int d = SPMV_GROUP / 2; d > 0; d >>= 1)
-    acc = __fadd_rn(acc, __shfl_xor(acc, d, wave_size));
-  return acc;
+  group_walk<true>(
+      rows, lo, hi, lane, [&](int32_t c) { return x[c]; },
+      [&](int32_t, float w, float v) { acc = __fmaf_rn(SCALED ? __fmul_rn(v, r) : v, w, acc); });
+  return group_butterfly(acc, [](float a, float b) { return __fadd_rn(a, b); });
 }
 
 /// Ends a TRACK kernel: the wavefront's largest magnitude, at most one atomic.
@@ -126,91 +77,48 @@ __device__ __forceinline__ void spmv_flush_max(unsigned worst, unsigned* max_bit
     atomicMax(max_bits, worst);
 }
 
-/// Once per call and row set: the rows of more than `segment` entries and their items.
-template <int header_only = 0>
-__global__ void __launch_bounds__(SPMV_BLOCK)
-    spmv_plan_kernel(spmv_rows_t rows, int32_t n, int32_t segment, spmv_plan_t plan) {
-  for (int64_t v = (int64_t)blockIdx.x * SPMV_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * SPMV_BLOCK) {
-    const int32_t d = rows.ap[v + 1] - rows.ap[v];
-    if (d <= segment)
-      continue;
-    const int32_t segments = (d + segment - 1) / segment;
-    const int32_t j = atomicAdd(&plan.counts[0], 1);
-    const int32_t at = atomicAdd(&plan.counts[1], segments);
-    if (j < plan.most_rows)  // sized from nnz, so both hold; they guard the stores all the same
-      plan.rows[j] = make_int2((int32_t)v, at);
-    for (int32_t k = 0; k < segments; ++k)
-      if (at + k < plan.most_items)
-        plan.items[at + k] = make_int2((int32_t)v, k);
-  }
-}
-
 /// y[v] for every row of at most `segment` entries, a lane group each.
 template <bool SCALED, bool TRACK>
-__global__ void __launch_bounds__(SPMV_BLOCK)
-    spmv_gather_kernel(spmv_rows_t rows, const float* x, const unsigned* scale_bits, int32_t n, int32_t segment,
+__global__ void __launch_bounds__(GROUP_BLOCK)
+    spmv_gather_kernel(csr_rows_t rows, const float* x, const unsigned* scale_bits, int32_t n, int32_t segment,
                        float* y, unsigned* max_bits) {
-  const int group = (int)threadIdx.x / SPMV_GROUP, lane = (int)threadIdx.x % SPMV_GROUP;
   const float r = SCALED ? spmv_reciprocal(scale_bits) : 1.0f;
   unsigned worst = 0;
-  // the offsets of the next row come in behind this row's entries
-  int32_t lo = 0, hi = 0;
-  if ((int64_t)blockIdx.x * SPMV_ROWS + group < n) {
-    lo = rows.ap[(int64_t)blockIdx.x * SPMV_ROWS + group];
-    hi = rows.ap[(int64_t)blockIdx.x * SPMV_ROWS + group + 1];
-  }
-  for (int64_t v0 = (int64_t)blockIdx.x * SPMV_ROWS; v0 < n; v0 += (int64_t)gridDim.x * SPMV_ROWS) {
-    const int64_t v = v0 + group, v_next = v + (int64_t)gridDim.x * SPMV_ROWS;
-    int32_t lo_next = 0, hi_next = 0;
-    if (v_next < n) {
-      lo_next = rows.ap[v_next];
-      hi_next = rows.ap[v_next + 1];
-    }
-    const bool mine = v < n && hi - lo <= segment;  // spmv_combine_kernel writes the longer rows
-    const float acc = spmv_group_sum<SCALED>(rows, x, r, lo, mine ? hi : lo, lane);
-    if (mine && lane == 0) {
-      y[v] = acc;
-      if (TRACK)
-        worst = max(worst, spmv_magnitude(acc));
-    }
-    lo = lo_next;
-    hi = hi_next;
-  }
+  group_sweep_rows(
+      rows.ap, n, segment, [](int64_t) { return 0; },
+      [&](int64_t v, int32_t lo, int32_t hi, bool, bool is_short, int, int lane) {
+        const float acc = spmv_group_sum<SCALED>(rows, x, r, lo, is_short ? hi : lo, lane);
+        if (is_short && lane == 0) {  // spmv_combine_kernel writes the longer rows
+          y[v] = acc;
+          if (TRACK)
+            worst = max(worst, spmv_magnitude(acc));
+        }
+      });
   if (TRACK)
     spmv_flush_max(worst, max_bits);
 }
 
 /// partial[i] = the sum over item i of the long rows, a lane group each.
 template <bool SCALED>
-__global__ void __launch_bounds__(SPMV_BLOCK)
-    spmv_segment_kernel(spmv_rows_t rows, const float* x, const unsigned* scale_bits, spmv_plan_t plan,
+__global__ void __launch_bounds__(GROUP_BLOCK)
+    spmv_segment_kernel(csr_rows_t rows, const float* x, const unsigned* scale_bits, group_plan_t plan,
                         int32_t segment, float* partial) {
-  const int group = (int)threadIdx.x / SPMV_GROUP, lane = (int)threadIdx.x % SPMV_GROUP;
-  const int32_t n_items = min(plan.counts[1], plan.most_items);
   const float r = SCALED ? spmv_reciprocal(scale_bits) : 1.0f;
-  for (int64_t i0 = (int64_t)blockIdx.x * SPMV_ROWS; i0 < n_items; i0 += (int64_t)gridDim.x * SPMV_ROWS) {
-    const int64_t i = i0 + group;
-    int32_t lo = 0, hi = 0;
-    if (i < n_items) {
-      const int2 item = plan.items[i];
-      const int64_t from = (int64_t)rows.ap[item.x] + (int64_t)item.y * segment;
-      lo = (int32_t)from;
-      hi = (int32_t)min((int64_t)rows.ap[item.x + 1], from + segment);
-    }
+  group_sweep_items(rows.ap, plan, segment, [&](int64_t i, int32_t, int32_t lo, int32_t hi, bool live, int lane) {
     const float acc = spmv_group_sum<SCALED>(rows, x, r, lo, hi, lane);
-    if (i < n_items && lane == 0)
+    if (live && lane == 0)
       partial[i] = acc;
-  }
+  });
 }
 
 /// y[v] of the long rows, a thread each: the partial sums in segment order.
 template <bool TRACK>
-__global__ void __launch_bounds__(SPMV_BLOCK)
-    spmv_combine_kernel(spmv_rows_t rows, spmv_plan_t plan, int32_t segment, const float* partial, float* y,
+__global__ void __launch_bounds__(GROUP_BLOCK)
+    spmv_combine_kernel(csr_rows_t rows, group_plan_t plan, int32_t segment, const float* partial, float* y,
                         unsigned* max_bits) {
   const int32_t n_long = min(plan.counts[0], plan.most_rows);
   unsigned worst = 0;
-  for (int64_t j = (int64_t)blockIdx.x * SPMV_BLOCK + threadIdx.x; j < n_long; j += (int64_t)gridDim.x * SPMV_BLOCK) {
+  for (int64_t j = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; j < n_long; j += (int64_t)gridDim.x * GROUP_BLOCK) {
     const int2 row = plan.rows[j];
     const int32_t segments = (rows.ap[row.x + 1] - rows.ap[row.x] + segment - 1) / segment;
     float acc = 0.0f;
@@ -227,8 +135,8 @@ __global__ void __launch_bounds__(SPMV_BLOCK)
 
 /// A call begins: h_0 = 1 in z[0] with h_max[0] = 1; everything else is 0.  z[0] has n entries.
 template <int header_only = 0>
-__global__ void __launch_bounds__(SPMV_BLOCK) hits_begin_kernel(float* z0, int32_t n, hits_ctl_t* ctl) {
-  for (int64_t v = (int64_t)blockIdx.x * SPMV_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * SPMV_BLOCK)
+__global__ void __launch_bounds__(GROUP_BLOCK) hits_begin_kernel(float* z0, int32_t n, hits_ctl_t* ctl) {
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * GROUP_BLOCK)
     z0[v] = 1.0f;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     ctl->a_max = ctl->a_last = ctl->h_max[1] = ctl->diff = 0;
@@ -241,13 +149,13 @@ __global__ void __launch_bounds__(SPMV_BLOCK) hits_begin_kernel(float* z0, int32
 
 /// max_v |h_t[v] - h_{t-1}[v]| into ctl->diff; `now` = t & 1.
 template <int header_only = 0>
-__global__ void __launch_bounds__(SPMV_BLOCK)
+__global__ void __launch_bounds__(GROUP_BLOCK)
     hits_residual_kernel(const float* z0, const float* z1, int now, int32_t n, hits_ctl_t* ctl) {
   const float* z_now = now ? z1 : z0;
   const float* z_old = now ? z0 : z1;
   const float r_now = spmv_reciprocal(&ctl->h_max[now]), r_old = spmv_reciprocal(&ctl->h_max[now ^ 1]);
   unsigned worst = 0;
-  for (int64_t v = (int64_t)blockIdx.x * SPMV_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * SPMV_BLOCK)
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * GROUP_BLOCK)
     worst = max(worst, spmv_magnitude(__fsub_rn(__fmul_rn(z_now[v], r_now), __fmul_rn(z_old[v], r_old))));
   spmv_flush_max(worst, &ctl->diff);
 }
@@ -274,14 +182,14 @@ __global__ void hits_step_kernel(hits_ctl_t* ctl, int32_t t, int measured, unsig
 /// Delivery: hub = z * r(h_max), authority = y * r(a_last), either may be NULL; counts the vertices
 /// with a value > 0 in one of them.
 template <int header_only = 0>
-__global__ void __launch_bounds__(SPMV_BLOCK)
+__global__ void __launch_bounds__(GROUP_BLOCK)
     hits_deliver_kernel(const float* z, const float* y, int now, int32_t n, float* hub, float* authority,
                         hits_ctl_t* ctl) {
   const float r_h = spmv_reciprocal(&ctl->h_max[now]), r_a = spmv_reciprocal(&ctl->a_last);
   unsigned count = 0;
-  const int64_t stride = (int64_t)gridDim.x * SPMV_BLOCK;
+  const int64_t stride = (int64_t)gridDim.x * GROUP_BLOCK;
   const int64_t span = ((int64_t)n + wave_size - 1) / wave_size * wave_size;  // whole wavefronts reach the ballot
-  for (int64_t v = (int64_t)blockIdx.x * SPMV_BLOCK + threadIdx.x; v < span; v += stride) {
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < span; v += stride) {
     float h = 0.0f, a = 0.0f;
     if (v < n) {
       h = __fmul_rn(z[v], r_h);

@@ -8,15 +8,15 @@
  * SSSP with ONE float32 add, the add every relaxation of grx_sssp performs, so at a fixed point the
  * equality holds bit for bit.  Two forms of the pass give the same answer:
  *
- *   pull   over in-rows.  A 16-lane group tests the entries of one vertex v (lane l entries l, l + 16,
- *          ..., TREE_FLIGHT loads in flight), keeps its smallest qualifying u, and the 16 minima meet
- *          in a butterfly; one lane stores pred[v] already mapped to source / -1 / -2.  No atomics.
+ *   pull   over in-rows.  A 16-lane group tests the entries of one vertex v (the sweep of
+ *          group_rows.hxx), each lane keeps its smallest qualifying u, and the 16 minima meet in the
+ *          butterfly; one lane stores pred[v] already mapped to source / -1 / -2.  No atomics.
  *   push   over out-rows.  pred starts at TREE_NONE; the group reads the owner's label once, skips the
  *          row of an unreached owner (it neither qualifies nor violates) and lowers pred[v] of every
  *          qualifying entry by a pre-tested atomicMin; tree_finalise_kernel maps what is left.
  *
- * Rows of more than `segment` entries are cut into items by spmv_plan_kernel (spmv_kernels.hxx) and a
- * group tests one item; in the pull form the items of a row meet by pre-tested atomicMin on pred[v],
+ * Rows of more than `segment` entries are cut into items by group_plan_kernel and a group tests one
+ * item; in the pull form the items of a row meet by pre-tested atomicMin on pred[v],
  * which tree_rows_kernel left at TREE_NONE, and tree_fixup_kernel maps the long rows.  A minimum, an
  * integer sum and a plain store do not depend on the order: a call repeats itself bit for bit.
  *
@@ -37,19 +37,13 @@
 
 #include <cfloat>
 
-#include <gunrock/hip/kernels/spmv_kernels.hxx>
+#include <gunrock/hip/kernels/group_rows.hxx>
 
 namespace gunrock {
 namespace hip {
 namespace kernels {
 
-constexpr int TREE_BLOCK = 256;
-constexpr int TREE_GROUP = 16;                        // lanes that share a row
-constexpr int TREE_ROWS = TREE_BLOCK / TREE_GROUP;    // rows a workgroup tests side by side
-constexpr int TREE_SEGMENT = 512;                     // default: row entries one lane group tests
-constexpr int TREE_SEGMENT_MIN = 64;
-constexpr int TREE_FLIGHT = 4;                        // entries in flight per lane
-constexpr int32_t TREE_NONE = INT32_MAX;              // pred[v] while no qualifying entry was seen
+constexpr int32_t TREE_NONE = INT32_MAX;  // pred[v] while no qualifying entry was seen
 constexpr int32_t TREE_UNREACHED = -1, TREE_ORPHAN = -2;
 
 /// The call's device words, 128 bytes apart.
@@ -105,65 +99,37 @@ __device__ __forceinline__ int32_t tree_deliver(int32_t v, int32_t source, bool 
 /**
  * @brief Entries [lo, hi) of `owner`'s row by one 16-lane group.  PUSH: the row is an out-row, the
  * owner (label `mine`, reached) is u and pred[] of the far end is lowered.  Pull: the row is an in-row,
- * the owner is v and the lane's smallest qualifying u lands in `best`.  Every lane of the wavefront
- * calls it (an empty range does nothing).
+ * the owner is v and the group's smallest qualifying u lands in `best`, in all its lanes.  Every lane of
+ * the wavefront calls it (an empty range does nothing).
  */
 template <typename label_t, bool PUSH>
-__device__ __forceinline__ void tree_group_walk(const spmv_rows_t& rows, const label_t* labels, int32_t owner,
-                                                label_t mine, int64_t lo, int64_t hi, int lane, int32_t* pred,
+__device__ __forceinline__ void tree_group_walk(const csr_rows_t& rows, const label_t* labels, int32_t owner,
+                                                label_t mine, int32_t lo, int32_t hi, int lane, int32_t* pred,
                                                 int32_t& best, unsigned long long& violations) {
   using rule = tree_rule_t<label_t>;
-  for (int64_t e = lo + lane; e < hi; e += TREE_GROUP * TREE_FLIGHT) {
-    int32_t c[TREE_FLIGHT];
-    float w[TREE_FLIGHT];
-    label_t far[TREE_FLIGHT];
-#pragma unroll
-    for (int k = 0; k < TREE_FLIGHT; ++k) {  // a slot past the end reads nothing
-      c[k] = 0;
-      w[k] = 0.0f;
-      if (e + k * TREE_GROUP < hi) {
-        c[k] = rows.aj[e + k * TREE_GROUP];
-        if (rule::weighted)
-          w[k] = rows.ax[e + k * TREE_GROUP];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < TREE_FLIGHT; ++k) {
-      far[k] = rule::unreached;
-      if (e + k * TREE_GROUP < hi)
-        far[k] = labels[c[k]];
-    }
-#pragma unroll
-    for (int k = 0; k < TREE_FLIGHT; ++k) {
-      if (e + k * TREE_GROUP >= hi)
-        continue;
-      bool qualifies = false, violates = false;
-      if (PUSH) {
-        rule::test(mine, w[k], far[k], qualifies, violates);
-        if (qualifies && load_relaxed(&pred[c[k]]) > owner)
-          atomicMin(&pred[c[k]], owner);
-      } else if (far[k] != rule::unreached) {
-        rule::test(far[k], w[k], mine, qualifies, violates);
-        if (qualifies)
-          best = min(best, c[k]);
-      }
-      violations += violates ? 1u : 0u;
-    }
-  }
-}
-
-/// The smallest `best` of a 16-lane group, valid in all its lanes.
-__device__ __forceinline__ int32_t tree_group_min(int32_t best) {
-#pragma unroll
-  for (int d = TREE_GROUP / 2; d > 0; d >>= 1)
-    best = min(best, __shfl_xor(best, d, wave_size));
-  return best;
+  group_walk<rule::weighted>(
+      rows, lo, hi, lane, [&](int32_t c) { return labels[c]; },
+      [&](int32_t c, float w, label_t far) {
+        bool qualifies = false, violates = false;
+        if (PUSH) {
+          rule::test(mine, w, far, qualifies, violates);
+          if (qualifies && load_relaxed(&pred[c]) > owner)
+            atomicMin(&pred[c], owner);
+        } else if (far != rule::unreached) {
+          rule::test(far, w, mine, qualifies, violates);
+          if (qualifies)
+            best = min(best, c);
+        }
+        violations += violates ? 1u : 0u;
+      });
+  if (!PUSH)
+    best = group_butterfly(best, [](int32_t a, int32_t b) { return min(a, b); });
 }
 
 /// Push form, first: pred[v] = TREE_NONE.
 template <int header_only = 0>
-__global__ void __launch_bounds__(TREE_BLOCK) tree_fill_kernel(int32_t* pred, int32_t n) {
-  for (int64_t v = (int64_t)blockIdx.x * TREE_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * TREE_BLOCK)
+__global__ void __launch_bounds__(GROUP_BLOCK) tree_fill_kernel(int32_t* pred, int32_t n) {
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * GROUP_BLOCK)
     pred[v] = TREE_NONE;
 }
 
@@ -174,46 +140,25 @@ __global__ void __launch_bounds__(TREE_BLOCK) tree_fill_kernel(int32_t* pred, in
  * Both count the violating entries they test.
  */
 template <typename label_t, bool PUSH>
-__global__ void __launch_bounds__(TREE_BLOCK)
-    tree_rows_kernel(spmv_rows_t rows, const label_t* labels, int32_t n, int32_t segment, int32_t source,
+__global__ void __launch_bounds__(GROUP_BLOCK)
+    tree_rows_kernel(csr_rows_t rows, const label_t* labels, int32_t n, int32_t segment, int32_t source,
                      int32_t* pred, unsigned long long* counts) {
   using rule = tree_rule_t<label_t>;
-  const int group = (int)threadIdx.x / TREE_GROUP, lane = (int)threadIdx.x % TREE_GROUP;
   unsigned long long reached = 0, orphans = 0, violations = 0;
-  // the offsets and the label of the next row come in behind this row's entries
-  int32_t lo = 0, hi = 0;
-  label_t mine = rule::unreached;
-  if ((int64_t)blockIdx.x * TREE_ROWS + group < n) {
-    lo = rows.ap[(int64_t)blockIdx.x * TREE_ROWS + group];
-    hi = rows.ap[(int64_t)blockIdx.x * TREE_ROWS + group + 1];
-    mine = labels[(int64_t)blockIdx.x * TREE_ROWS + group];
-  }
-  for (int64_t v0 = (int64_t)blockIdx.x * TREE_ROWS; v0 < n; v0 += (int64_t)gridDim.x * TREE_ROWS) {
-    const int64_t v = v0 + group, v_next = v + (int64_t)gridDim.x * TREE_ROWS;
-    int32_t lo_next = 0, hi_next = 0;
-    label_t mine_next = rule::unreached;
-    if (v_next < n) {
-      lo_next = rows.ap[v_next];
-      hi_next = rows.ap[v_next + 1];
-      mine_next = labels[v_next];
-    }
-    const bool is_reached = v < n && mine != rule::unreached;
-    const bool is_short = v < n && hi - lo <= segment;
-    // an out-row of an unreached owner neither qualifies nor violates; an in-row of one can violate
-    const bool walk = is_short && (!PUSH || is_reached);
-    int32_t best = TREE_NONE;
-    tree_group_walk<label_t, PUSH>(rows, labels, (int32_t)v, mine, lo, walk ? hi : lo, lane, pred, best, violations);
-    if (!PUSH) {
-      best = tree_group_min(best);
-      if (v < n && lane == 0) {
-        reached += is_reached ? 1u : 0u;
-        pred[v] = is_short ? tree_deliver((int32_t)v, source, is_reached, best, orphans) : TREE_NONE;
-      }
-    }
-    lo = lo_next;
-    hi = hi_next;
-    mine = mine_next;
-  }
+  group_sweep_rows(
+      rows.ap, n, segment, [&](int64_t v) { return labels[v]; },
+      [&](int64_t v, int32_t lo, int32_t hi, bool in_range, bool is_short, label_t mine, int lane) {
+        const bool is_reached = in_range && mine != rule::unreached;
+        // an out-row of an unreached owner neither qualifies nor violates; an in-row of one can violate
+        const bool walk = is_short && (!PUSH || is_reached);
+        int32_t best = TREE_NONE;
+        tree_group_walk<label_t, PUSH>(rows, labels, (int32_t)v, mine, lo, walk ? hi : lo, lane, pred, best,
+                                       violations);
+        if (!PUSH && in_range && lane == 0) {
+          reached += is_reached ? 1u : 0u;
+          pred[v] = is_short ? tree_deliver((int32_t)v, source, is_reached, best, orphans) : TREE_NONE;
+        }
+      });
   if (!PUSH) {
     tree_flush(reached, &counts[TREE_N_REACHED]);
     tree_flush(orphans, &counts[TREE_N_ORPHANS]);
@@ -223,46 +168,30 @@ __global__ void __launch_bounds__(TREE_BLOCK)
 
 /// Every item of the long rows, a lane group each.  Pull: the items of a row meet in pred[v].
 template <typename label_t, bool PUSH>
-__global__ void __launch_bounds__(TREE_BLOCK)
-    tree_segment_kernel(spmv_rows_t rows, const label_t* labels, spmv_plan_t plan, int32_t segment, int32_t* pred,
+__global__ void __launch_bounds__(GROUP_BLOCK)
+    tree_segment_kernel(csr_rows_t rows, const label_t* labels, group_plan_t plan, int32_t segment, int32_t* pred,
                         unsigned long long* counts) {
   using rule = tree_rule_t<label_t>;
-  const int group = (int)threadIdx.x / TREE_GROUP, lane = (int)threadIdx.x % TREE_GROUP;
-  const int32_t n_items = min(plan.counts[1], plan.most_items);
   unsigned long long violations = 0;
-  for (int64_t i0 = (int64_t)blockIdx.x * TREE_ROWS; i0 < n_items; i0 += (int64_t)gridDim.x * TREE_ROWS) {
-    const int64_t i = i0 + group;
-    int64_t lo = 0, hi = 0;
-    int32_t v = 0;
-    label_t mine = rule::unreached;
-    if (i < n_items) {
-      const int2 item = plan.items[i];
-      v = item.x;
-      mine = labels[v];
-      if (!PUSH || mine != rule::unreached) {
-        lo = (int64_t)rows.ap[v] + (int64_t)item.y * segment;
-        hi = min((int64_t)rows.ap[v + 1], lo + segment);
-      }
-    }
+  group_sweep_items(rows.ap, plan, segment, [&](int64_t, int32_t v, int32_t lo, int32_t hi, bool live, int lane) {
+    const label_t mine = live ? labels[v] : rule::unreached;
+    const bool walk = !PUSH || mine != rule::unreached;  // as in tree_rows_kernel
     int32_t best = TREE_NONE;
-    tree_group_walk<label_t, PUSH>(rows, labels, v, mine, lo, hi, lane, pred, best, violations);
-    if (!PUSH) {
-      best = tree_group_min(best);
-      if (i < n_items && lane == 0 && best != TREE_NONE && load_relaxed(&pred[v]) > best)
-        atomicMin(&pred[v], best);
-    }
-  }
+    tree_group_walk<label_t, PUSH>(rows, labels, v, mine, lo, walk ? hi : lo, lane, pred, best, violations);
+    if (!PUSH && live && lane == 0 && best != TREE_NONE && load_relaxed(&pred[v]) > best)
+      atomicMin(&pred[v], best);
+  });
   tree_flush(violations, &counts[TREE_N_VIOLATIONS]);
 }
 
 /// Pull form, last: the long rows' pred[v], a thread each, from what their items left.
 template <typename label_t>
-__global__ void __launch_bounds__(TREE_BLOCK)
-    tree_fixup_kernel(const label_t* labels, spmv_plan_t plan, int32_t source, int32_t* pred,
+__global__ void __launch_bounds__(GROUP_BLOCK)
+    tree_fixup_kernel(const label_t* labels, group_plan_t plan, int32_t source, int32_t* pred,
                       unsigned long long* counts) {
   const int32_t n_long = min(plan.counts[0], plan.most_rows);
   unsigned long long orphans = 0;
-  for (int64_t j = (int64_t)blockIdx.x * TREE_BLOCK + threadIdx.x; j < n_long; j += (int64_t)gridDim.x * TREE_BLOCK) {
+  for (int64_t j = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; j < n_long; j += (int64_t)gridDim.x * GROUP_BLOCK) {
     const int32_t v = plan.rows[j].x;
     pred[v] = tree_deliver(v, source, labels[v] != tree_rule_t<label_t>::unreached, pred[v], orphans);
   }
@@ -271,10 +200,10 @@ __global__ void __launch_bounds__(TREE_BLOCK)
 
 /// Push form, last: every pred[v], a thread each; counts the reached labels and the orphans.
 template <typename label_t>
-__global__ void __launch_bounds__(TREE_BLOCK)
+__global__ void __launch_bounds__(GROUP_BLOCK)
     tree_finalise_kernel(const label_t* labels, int32_t n, int32_t source, int32_t* pred, unsigned long long* counts) {
   unsigned long long reached = 0, orphans = 0;
-  for (int64_t v = (int64_t)blockIdx.x * TREE_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * TREE_BLOCK) {
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * GROUP_BLOCK) {
     const bool is_reached = labels[v] != tree_rule_t<label_t>::unreached;
     reached += is_reached ? 1u : 0u;
     pred[v] = tree_deliver((int32_t)v, source, is_reached, pred[v], orphans);
@@ -285,8 +214,8 @@ __global__ void __launch_bounds__(TREE_BLOCK)
 
 /// Hops begin: a vertex with a predecessor other than itself is one step from it; all others end a chain.
 template <int header_only = 0>
-__global__ void __launch_bounds__(TREE_BLOCK) tree_hops_begin_kernel(const int32_t* pred, int32_t n, int2* pair) {
-  for (int64_t v = (int64_t)blockIdx.x * TREE_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * TREE_BLOCK) {
+__global__ void __launch_bounds__(GROUP_BLOCK) tree_hops_begin_kernel(const int32_t* pred, int32_t n, int2* pair) {
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * GROUP_BLOCK) {
     const int32_t p = pred[v];
     pair[v] = p >= 0 && p != (int32_t)v ? make_int2(p, 1) : make_int2((int32_t)v, 0);
   }
@@ -294,10 +223,10 @@ __global__ void __launch_bounds__(TREE_BLOCK) tree_hops_begin_kernel(const int32
 
 /// One doubling round from `old` into `now`; leaves 1 in *changed when a pair moved.
 template <int header_only = 0>
-__global__ void __launch_bounds__(TREE_BLOCK)
+__global__ void __launch_bounds__(GROUP_BLOCK)
     tree_hops_round_kernel(const int2* old, int2* now, int32_t n, unsigned long long* changed) {
   bool moved = false;
-  for (int64_t v = (int64_t)blockIdx.x * TREE_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * TREE_BLOCK) {
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * GROUP_BLOCK) {
     int2 p = old[v];
     const int2 q = old[p.x];
     if (q.x != p.x) {  // the ancestor is not the end of its chain
@@ -323,9 +252,9 @@ __global__ void tree_hops_publish_kernel(unsigned long long* changed, unsigned l
 
 /// Hops end: the steps of a vertex whose chain ends at the source, -1 for every other.
 template <int header_only = 0>
-__global__ void __launch_bounds__(TREE_BLOCK)
+__global__ void __launch_bounds__(GROUP_BLOCK)
     tree_hops_end_kernel(const int2* pair, int32_t n, int32_t source, int32_t* hops) {
-  for (int64_t v = (int64_t)blockIdx.x * TREE_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * TREE_BLOCK) {
+  for (int64_t v = (int64_t)blockIdx.x * GROUP_BLOCK + threadIdx.x; v < n; v += (int64_t)gridDim.x * GROUP_BLOCK) {
     const int2 p = pair[v];
     hops[v] = p.x == source ? p.y : -1;
   }

@@ -2,7 +2,8 @@
 numpy float64.  The checker, never the thing shipped."""
 import numpy as np
 
-from ppr_oracle import csr, transpose  # noqa: F401  (the tests build their inputs with these)
+# the tests build their inputs with these
+from ppr_oracle import SWEEP_LENGTHS, csr, sweep_ladder, transpose  # noqa: F401
 
 ULP = 2.0 ** -24
 

@@ -31,6 +31,25 @@ def transpose(ap, aj, aw):
     return np.cumsum(tp).astype(np.int32), src[order].astype(np.int32), np.asarray(aw)[order]
 
 
+SWEEP_LENGTHS = [0, 1, 15, 16, 17, 63, 64, 65, 128, 129, 200]
+
+
+def sweep_ladder():
+    """The edge conditions of the lane-group row sweep at one tiny shape: a directed multigraph of 37
+    vertices (no multiple of the 16 rows a workgroup walks side by side) whose out-rows AND in-rows have
+    every length of SWEEP_LENGTHS -- around the group of 16, around a segment of 64 (64 is short, 65 is
+    two items with a one-entry tail, 200 ends in a partial item) and none.  Vertex v < 11 has
+    SWEEP_LENGTHS[v] out-entries and SWEEP_LENGTHS[(v + 2) % 11] in-entries: vertex 10 (200 out) is the
+    source of the searches, vertex 9 (129 out, none in) is unreached with a long out-row.  The other
+    26 vertices have 3 of each.  Weights are integers in [1, 8].  -> (ap, aj, aw)"""
+    rng = np.random.default_rng(29)
+    out_degree = np.array(SWEEP_LENGTHS + [3] * 26)
+    in_degree = np.array([SWEEP_LENGTHS[(v + 2) % 11] for v in range(11)] + [3] * 26)
+    tails = np.repeat(np.arange(37), out_degree)
+    heads = rng.permutation(np.repeat(np.arange(37), in_degree))
+    return csr(37, np.stack([tails, heads], axis=1), rng.integers(1, 9, len(tails)), symmetric=False)
+
+
 def _setup(ap, aj, aw, alpha, in_edges):
     ap, aj = np.asarray(ap, np.int64), np.asarray(aj, np.int64)
     aw = np.asarray(aw, np.float32).astype(np.float64)

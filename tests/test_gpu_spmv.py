@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from hits_oracle import csr, spmv, transpose
+from hits_oracle import SWEEP_LENGTHS, csr, spmv, sweep_ladder, transpose
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
 
@@ -104,6 +104,25 @@ def test_exact_on_a_rectangular_ladder(ea, ctx, ladder, monkeypatch, segment):
     want = exact(spmv(ap, aj, aw, x))
     assert (y == want).all(), (y, want)
     assert y[0] == 0 and (y[1:] > 0).all()
+
+
+@pytest.mark.parametrize("segment", [None, "64"])
+def test_exact_on_the_sweep_ladder(ea, ctx, monkeypatch, segment):
+    """37 rows, out-rows forward and in-rows transposed: the last sweep of a workgroup has lane groups
+    past the end, and under the hook a row of 64 is short, 65 leaves an item of one entry and 200 a
+    partial last item; by default nothing is long but the plan still runs (776 entries)."""
+    ap, aj, aw = sweep_ladder()
+    for offsets in (ap, transpose(ap, aj, aw)[0]):
+        assert len(offsets) == 38 and set(SWEEP_LENGTHS) <= set(np.diff(offsets).tolist())
+    g = ea.Graph.from_host_csr(ap, aj, aw).build_in_edges(ctx)
+    x = integers(np.random.default_rng(8), 37)
+    if segment:
+        monkeypatch.setenv("GRX_SPMV_SEGMENT", segment)
+    forward, st = twice(ea, ctx, g, x)
+    back, st_back = twice(ea, ctx, g, x, transpose=True)
+    assert (forward == exact(spmv(ap, aj, aw, x))).all()
+    assert (back == exact(spmv(ap, aj, aw, x, transpose=True))).all()
+    assert st.advance_launches == st_back.advance_launches == 4
 
 
 def test_a_graph_below_one_segment_plans_nothing(ea, ctx):

@@ -7,7 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tree_oracle import FLT_UNREACHED, INT_UNREACHED, csr, doubling_rounds, entries, tree
+from tree_oracle import (FLT_UNREACHED, INT_UNREACHED, SWEEP_LENGTHS, csr, doubling_rounds, entries, sweep_ladder,
+                         transpose, tree)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(600)]
 
@@ -394,3 +395,36 @@ def test_labels_of_the_hot_first_copy_in_the_callers_numbering(ea, ctx):
         assert st.pull_iterations == 1
     u, v, qualifies, _ = entries(c.ap, c.aj, c.aw, c.host["sssp"])
     assert qualifies.sum() >= c.want["sssp"]["reached"] - 1
+
+
+# ---- 11. the edges of the row sweep at one tiny shape --------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def ladder(ea, ctx):
+    ap, aj, aw = sweep_ladder()
+    for offsets in (ap, transpose(ap, aj, aw)[0]):
+        assert len(offsets) == 38 and set(SWEEP_LENGTHS) <= set(np.diff(offsets).tolist())
+    c = Case(ea, ctx, ea.Graph.from_host_csr(ap, aj, aw), source=10)  # the labels of the graph as given
+    c.g.build_in_edges(ctx)
+    return c
+
+
+@pytest.mark.parametrize("segment", [None, "64"])
+@pytest.mark.parametrize("pull", [True, False], ids=["pull", "push"])
+@pytest.mark.parametrize("kind", ["bfs", "sssp"])
+def test_sweep_ladder(ea, ctx, ladder, monkeypatch, kind, pull, segment):
+    """37 vertices, in-rows pulled and out-rows pushed: the last sweep of a workgroup has lane groups
+    past the end, and under the hook a row of 64 is short, 65 leaves an item of one entry and 200 a
+    partial last item.  Vertex 9 has no in-entry: unreached, and its 129 out-entries are items that
+    the push form must skip."""
+    c = ladder
+    want = c.want[kind]
+    assert want["pred"][9] == -1 and want["violations"] == 0 and 20 < want["reached"] < 37
+    if not pull:
+        monkeypatch.setenv("GRX_TREE_PULL", "0")
+    if segment:
+        monkeypatch.setenv("GRX_TREE_SEGMENT", segment)
+    _, _, _, st = twice(ea, ctx, c.g, c.source, c.labels[kind], hops=kind == "sssp", want=want)
+    assert st.pull_iterations == int(pull)
+    hops_launches = 0 if kind == "bfs" else 2 + 5 * ((st.iterations + 1 + 3) // 4)
+    assert st.advance_launches - hops_launches == (4 if pull else 5)  # 776 entries: the plan always runs

@@ -2,7 +2,8 @@
 followed literally in numpy.  The checker, never the thing shipped."""
 import numpy as np
 
-from ppr_oracle import csr, transpose  # noqa: F401  (the tests build their inputs with these)
+# the tests build their inputs with these
+from ppr_oracle import SWEEP_LENGTHS, csr, sweep_ladder, transpose  # noqa: F401
 
 INT_UNREACHED = 2 ** 31 - 1
 FLT_UNREACHED = np.finfo(np.float32).max
