@@ -230,6 +230,8 @@ _SIGNATURES = {
     "grx_ppr": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_float, C.c_float, _VP, _VP, _VP, C.POINTER(_Options),
                           C.POINTER(_Stats)]),
     "grx_spmv": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_spmm": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(_Options),
+                           C.POINTER(_Stats)]),
     "grx_hits": (C.c_int, [_VP, _VP, C.c_float, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_bfs_predecessors": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -1076,6 +1078,75 @@ def spmv(ctx: Context, g: Graph, x, transpose: bool = False, y=None, options: Op
     _check(load_library().grx_spmv(ctx._h, g._h, int(bool(transpose)), _ptr(x) if x.numel() else None,
                                    _ptr(y) if y.numel() else None, C.byref(o), C.byref(s)), "grx_spmv")
     return y, Stats._from(s)
+
+
+def _float_matrix(ctx: Context, t, rows: int, features: Optional[int], call: str, what: str):
+    """The float32 matrix `what` of `call` -> (tensor, its leading dimension in elements): allocated
+    contiguous when None, else checked to be a 2-D tensor of `rows` rows (and `features` columns when
+    given) on the context's device whose rows are contiguous and do not run into each other."""
+    torch = _torch()
+    device = torch.device(f"cuda:{ctx.device}")
+    if t is None:
+        t = torch.empty((rows, features), dtype=torch.float32, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"{call}: {what} must be a float32 torch tensor")
+    if t.dim() != 2 or t.shape[0] != rows or (features is not None and t.shape[1] != features):
+        shape = f"{rows} x {'F' if features is None else features}"
+        raise ValueError(f"{call}: {what} must be a 2-D tensor of {shape} elements")
+    F = t.shape[1]
+    # a stride of a dimension of one element (or none) addresses nothing
+    if (F > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < F):
+        raise ValueError(f"{call}: {what} must have stride(1) == 1 and stride(0) >= {F}")
+    if t.device != device:
+        raise ValueError(f"{call}: {what} must live on {device}")
+    return t, (max(t.stride(0), F) if rows > 1 else F)
+
+
+def spmm(ctx: Context, g: Graph, x, transpose: bool = False, y=None, options: Optional[Options] = None):
+    """Y = A X over the graph's entries for a dense feature matrix, or Y = A^T X -> (float32 Y on
+    the device, Stats).
+
+    `x`: float32 2-D tensor on the context's device of n_cols rows (n_rows when transposed) and F
+    columns with stride(1) == 1 and stride(0) >= F: row-strided views are accepted as they are.  `y`:
+    the same of n_rows (n_cols) rows and F columns, allocated contiguous when None; its columns
+    [0, F) are overwritten, what lies between its rows is neither read nor written; the two must not
+    overlap.  Every element is summed over its row's entries in row order, rows above
+    GRX_SPMM_SEGMENT = 512 entries in segments whose sums are added in order: the same call returns
+    identical bits, column f is bit for bit the F = 1 call on that column, and the value is exact
+    whenever float32 holds every partial sum (include/essentials_amd.h).  The transposed product is a
+    pull over in-rows under `spmv`'s rule: a directed graph needs its in-edges
+    (`g.build_in_edges(ctx)`), an asymmetric CSR without them and a rectangular graph raise
+    EngineError.  The engine's stream waits for what torch has enqueued.  Options read:
+    collect_kernel_time."""
+    if x is None:
+        raise TypeError("spmm: x must be a float32 torch tensor")
+    x, ldx = _float_matrix(ctx, x, g.n_rows if transpose else g.n_cols, None, "spmm", "x")
+    F = x.shape[1]
+    y, ldy = _float_matrix(ctx, y, g.n_cols if transpose else g.n_rows, F, "spmm", "y")
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_spmm(ctx._h, g._h, int(bool(transpose)), F, _ptr(x) if x.numel() else None, ldx,
+                                   _ptr(y) if y.numel() else None, ldy, C.byref(o), C.byref(s)), "grx_spmm")
+    return y, Stats._from(s)
+
+
+def spmm_autograd(ctx: Context, g: Graph, x):
+    """`spmm(ctx, g, x)[0]` as a differentiable function of `x`: the backward pass is the transposed
+    product of the incoming gradient, so it raises at backward time whatever
+    `spmm(..., transpose=True)` raises on this graph.  The graph's values are constants."""
+    torch = _torch()
+
+    class _Product(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, features):
+            return spmm(ctx, g, features)[0]
+
+        @staticmethod
+        def backward(fctx, grad):
+            return spmm(ctx, g, grad.contiguous(), transpose=True)[0]
+
+    return _Product.apply(x)
 
 
 def hits(ctx: Context, g: Graph, tol: float = 1e-6, hubs=None, authorities=None, normalized: bool = False,

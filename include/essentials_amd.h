@@ -855,6 +855,56 @@ int grx_ppr(grx_context_t ctx, grx_graph_t g, const int32_t* h_seeds, int32_t n_
  * sum per segment). */
 int grx_spmv(grx_context_t ctx, grx_graph_t g, int32_t transpose, const float* d_x, float* d_y,
              const grx_options* opt, grx_stats* stats);
+/* Sparse-dense product Y = A X over the handle's entries for a dense feature matrix, every output
+ * element summed in a written order: the aggregation step of a message-passing layer, and with
+ * transpose its backward pass.  An addition: the reference has an experiment of this
+ * (examples/experiments/spmm.cu) and no algorithm header.
+ * F = n_features.  Both matrices are row-major float32: row i of X starts at d_x + i * ldx and row i
+ * of Y at d_y + i * ldy, with ldx, ldy >= F in elements.
+ * transpose == 0: Y[r, f] = sum over entries (r -> c, w) of row r of X[c, f] * w; X has n_cols rows
+ * and Y has n_rows rows; a rectangular graph is allowed.
+ * transpose != 0: Y[c, f] = sum over entries (r -> c, w) of X[r, f] * w, as a PULL over in-rows,
+ * never a scatter, under grx_spmv's rule: with in-edges attached (grx_graph_build_in_edges) over
+ * those arrays and their values; without them over the handle's own rows when the CSR is symmetric
+ * (an unknown verdict is verified first); an asymmetric CSR without in-edges is GRX_ERR_UNSUPPORTED
+ * and the message names grx_graph_build_in_edges.  transpose != 0 with n_rows != n_cols is
+ * GRX_ERR_UNSUPPORTED.
+ * What is written: columns [0, F) of every row of Y are overwritten, an empty row gives 0.0f in all
+ * of them.  Columns [F, ldy) of Y are never written and never read, and neither are [F, ldx) of X.
+ * Weights and features are read as they are: a zero weight times an infinite feature is NaN and is
+ * delivered as such; no entry is skipped for its weight.
+ * Summation order (the reproducibility contract): no float atomics.  With S = GRX_SPMM_SEGMENT
+ * (default 512, minimum 64; an environment variable read per call, a test hook) and a fixed output
+ * element, the row's entries are cut into segments of S consecutive entries, the last one may be
+ * shorter.  A segment's partial sum starts from 0.0f and takes its entries IN ROW ORDER, one fused
+ * multiply-add each: acc = fma(X[c, f], w, acc).  A row of at most S entries delivers that sum; a
+ * longer row delivers ((p0 + p1) + p2) + ... in segment order with plain float32 adds.  The order is
+ * a function of the row's layout and S alone: it does not depend on F, ldx, ldy, the pointers'
+ * alignment, the grid, the CU count or arrival order.  So two calls return the same bits; column f
+ * of an F-wide call is bit-identical to the F = 1 call on that column; and where every term and
+ * every partial sum is representable in float32 the result is the exact value.  The order is NOT
+ * grx_spmv's (16 interleaved lanes and a butterfly): the two calls agree bit for bit only where both
+ * are exact.
+ * F == 0, or an output without rows, is GRX_OK: nothing is launched, stats (when given) is zeroed.
+ * GRX_ERR_INVALID_ARGUMENT, found on the host before anything is launched, each message naming
+ * grx_spmm: a NULL ctx or g; n_features < 0; ldx < F or ldy < F; a NULL d_x or d_y whose matrix has
+ * elements; the byte range of X overlapping that of Y (the message says "overlap"), a range being
+ * first element to last element, (rows - 1) * ld + F elements long -- two interleaved views of one
+ * buffer overlap in this sense although they share no element.
+ * opt may be NULL; only collect_kernel_time is read.  stats may be NULL; set: elapsed_ms,
+ * advance_kernel_ms (with collect_kernel_time), advance_launches (kernel launches: 1 for a graph of
+ * at most S entries, otherwise 4 -- the plan, the short rows, the segments, their sums),
+ * iterations = 1, edges_traversed = edges_expanded = nnz; everything else 0.
+ * The call runs on the caller's CSR and numbering as given, builds and uses no hot-first copy, leaves
+ * nothing on the handle but a symmetry verdict and releases its workspace when it returns: none for a
+ * graph of at most S entries, otherwise 32 bytes per S entries of the graph (the lists of long rows
+ * and their segments) and 4 F bytes per segment the lists have room for (the partial sums).
+ * Every element offset into X and Y (row * ld + f) is computed in 64 bits: n_rows * ldy may exceed
+ * 2^31.  Accesses are 16 bytes wide where the base pointer is 16-byte aligned and ld % 4 == 0, and
+ * narrower otherwise; the result does not depend on it. */
+int grx_spmm(grx_context_t ctx, grx_graph_t g, int32_t transpose, int32_t n_features,
+             const float* d_x, int64_t ldx, float* d_y, int64_t ldy,
+             const grx_options* opt, grx_stats* stats);
 /* HITS: hub and authority scores by power iteration, two pull products per iteration.  It REPLACES
  * the reference's hits.hxx rather than wrapping it: that client does one float atomic per edge in each
  * direction, normalises by an L2 norm and stops on bit-equality of two vectors, so it neither repeats
