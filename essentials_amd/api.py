@@ -232,6 +232,10 @@ _SIGNATURES = {
     "grx_spmv": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_spmm": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(_Options),
                            C.POINTER(_Stats)]),
+    "grx_spmm_values": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int64, _VP, C.c_int64,
+                                  C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_sddmm": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int64, _VP, C.c_int64, _VP, C.POINTER(_Options),
+                            C.POINTER(_Stats)]),
     "grx_hits": (C.c_int, [_VP, _VP, C.c_float, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_bfs_predecessors": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -1102,7 +1106,8 @@ def _float_matrix(ctx: Context, t, rows: int, features: Optional[int], call: str
     return t, (max(t.stride(0), F) if rows > 1 else F)
 
 
-def spmm(ctx: Context, g: Graph, x, transpose: bool = False, y=None, options: Optional[Options] = None):
+def spmm(ctx: Context, g: Graph, x, transpose: bool = False, y=None, options: Optional[Options] = None,
+         values=None):
     """Y = A X over the graph's entries for a dense feature matrix, or Y = A^T X -> (float32 Y on
     the device, Stats).
 
@@ -1117,36 +1122,126 @@ def spmm(ctx: Context, g: Graph, x, transpose: bool = False, y=None, options: Op
     pull over in-rows under `spmv`'s rule: a directed graph needs its in-edges
     (`g.build_in_edges(ctx)`), an asymmetric CSR without them and a rectangular graph raise
     EngineError.  The engine's stream waits for what torch has enqueued.  Options read:
-    collect_kernel_time."""
+    collect_kernel_time.
+
+    `values`: None multiplies by the values the graph was built with (grx_spmm).  Otherwise a
+    contiguous float32 tensor of nnz elements on the context's device, in the order of the CSR's
+    entries, takes their place (grx_spmm_values); it must not overlap `y`, and the result has the bits
+    of `spmm` on a graph built from the same structure with those values.  With `values` the
+    transposed product needs the in-edges on every graph, a symmetric one included."""
     if x is None:
         raise TypeError("spmm: x must be a float32 torch tensor")
+    if values is not None:
+        values = _float_vector(ctx, values, g.nnz, "spmm", "values")
     x, ldx = _float_matrix(ctx, x, g.n_rows if transpose else g.n_cols, None, "spmm", "x")
     F = x.shape[1]
     y, ldy = _float_matrix(ctx, y, g.n_cols if transpose else g.n_rows, F, "spmm", "y")
     o = (options or Options())._c()
     s = _Stats()
     ctx.after_torch()
-    _check(load_library().grx_spmm(ctx._h, g._h, int(bool(transpose)), F, _ptr(x) if x.numel() else None, ldx,
-                                   _ptr(y) if y.numel() else None, ldy, C.byref(o), C.byref(s)), "grx_spmm")
+    px, py = _ptr(x) if x.numel() else None, _ptr(y) if y.numel() else None
+    if values is None:
+        _check(load_library().grx_spmm(ctx._h, g._h, int(bool(transpose)), F, px, ldx, py, ldy, C.byref(o),
+                                       C.byref(s)), "grx_spmm")
+    else:
+        _check(load_library().grx_spmm_values(ctx._h, g._h, _ptr(values) if values.numel() else None,
+                                              int(bool(transpose)), F, px, ldx, py, ldy, C.byref(o), C.byref(s)),
+               "grx_spmm_values")
     return y, Stats._from(s)
 
 
-def spmm_autograd(ctx: Context, g: Graph, x):
-    """`spmm(ctx, g, x)[0]` as a differentiable function of `x`: the backward pass is the transposed
-    product of the incoming gradient, so it raises at backward time whatever
-    `spmm(..., transpose=True)` raises on this graph.  The graph's values are constants."""
+def sddmm(ctx: Context, g: Graph, u, v, out=None, options: Optional[Options] = None):
+    """out[e] = <u[row(e)], v[col(e)]> for every entry e of the graph's CSR, at the entry's position in
+    the column array -> (float32 out of nnz elements on the device, Stats).
+
+    `u`: float32 2-D tensor on the context's device of n_rows rows and F columns, `v`: of n_cols rows
+    and F columns, both with stride(1) == 1 and stride(0) >= F (row-strided views are accepted as they
+    are); they may be the same tensor.  `out`: contiguous float32 of nnz elements, allocated when None,
+    overwritten in full; it must not overlap `u` or `v`.  The graph's values are not read.  Every dot
+    product is summed in an order that depends on F alone (include/essentials_amd.h): the same call
+    returns identical bits, and the exact value whenever float32 holds every partial sum.  The engine's
+    stream waits for what torch has enqueued.  Options read: collect_kernel_time."""
+    if u is None or v is None:
+        raise TypeError("sddmm: u and v must be float32 torch tensors")
+    u, ldu = _float_matrix(ctx, u, g.n_rows, None, "sddmm", "u")
+    F = u.shape[1]
+    v, ldv = _float_matrix(ctx, v, g.n_cols, F, "sddmm", "v")
+    out = _float_vector(ctx, out, g.nnz, "sddmm", "out")
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_sddmm(ctx._h, g._h, F, _ptr(u) if u.numel() else None, ldu,
+                                    _ptr(v) if v.numel() else None, ldv, _ptr(out) if out.numel() else None,
+                                    C.byref(o), C.byref(s)), "grx_sddmm")
+    return out, Stats._from(s)
+
+
+def spmm_autograd(ctx: Context, g: Graph, x, values=None):
+    """`spmm(ctx, g, x, values=values)[0]` as a differentiable function: the backward pass is the
+    transposed product of the incoming gradient, so it raises at backward time whatever
+    `spmm(..., transpose=True)` raises on this graph.  Without `values` the graph's values are
+    constants and `x` is the one input.  With `values` (the per-entry values of `spmm`) the function is
+    differentiable in both: grad_x = spmm(grad, values=values, transpose=True), which needs the
+    in-edges, and grad_values = sddmm(grad, x); each is computed only where a gradient is asked for."""
     torch = _torch()
 
-    class _Product(torch.autograd.Function):
+    if values is None:
+        class _Product(torch.autograd.Function):
+            @staticmethod
+            def forward(fctx, features):
+                return spmm(ctx, g, features)[0]
+
+            @staticmethod
+            def backward(fctx, grad):
+                return spmm(ctx, g, grad.contiguous(), transpose=True)[0]
+
+        return _Product.apply(x)
+
+    class _WeightedProduct(torch.autograd.Function):
         @staticmethod
-        def forward(fctx, features):
-            return spmm(ctx, g, features)[0]
+        def forward(fctx, features, w):
+            fctx.save_for_backward(features, w)
+            return spmm(ctx, g, features, values=w)[0]
 
         @staticmethod
         def backward(fctx, grad):
-            return spmm(ctx, g, grad.contiguous(), transpose=True)[0]
+            features, w = fctx.saved_tensors
+            grad = grad.contiguous()
+            grad_x = grad_w = None
+            if fctx.needs_input_grad[0]:
+                grad_x = spmm(ctx, g, grad, values=w, transpose=True)[0]
+            if fctx.needs_input_grad[1]:
+                grad_w = sddmm(ctx, g, grad, features)[0]
+            return grad_x, grad_w
 
-    return _Product.apply(x)
+    return _WeightedProduct.apply(x, values)
+
+
+def sddmm_autograd(ctx: Context, g: Graph, u, v):
+    """`sddmm(ctx, g, u, v)[0]` as a differentiable function of `u` and `v`: grad_u =
+    spmm(v, values=grad) and grad_v = spmm(u, values=grad, transpose=True), each computed only where a
+    gradient is asked for.  The backward pass raises whatever those calls raise: grad_v needs the
+    graph's in-edges (`g.build_in_edges(ctx)`) and a square graph."""
+    torch = _torch()
+
+    class _Scores(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, left, right):
+            fctx.save_for_backward(left, right)
+            return sddmm(ctx, g, left, right)[0]
+
+        @staticmethod
+        def backward(fctx, grad):
+            left, right = fctx.saved_tensors
+            grad = grad.contiguous()
+            grad_u = grad_v = None
+            if fctx.needs_input_grad[0]:
+                grad_u = spmm(ctx, g, right, values=grad)[0]
+            if fctx.needs_input_grad[1]:
+                grad_v = spmm(ctx, g, left, values=grad, transpose=True)[0]
+            return grad_u, grad_v
+
+    return _Scores.apply(u, v)
 
 
 def hits(ctx: Context, g: Graph, tol: float = 1e-6, hubs=None, authorities=None, normalized: bool = False,

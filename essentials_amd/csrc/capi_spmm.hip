@@ -1,9 +1,12 @@
 /** @file capi_spmm.hip  grx_spmm: the sparse-dense product Y = A X (hip/kernels/spmm_kernels.hxx), features on
  * the lanes and a row's entries in row order, long rows cut into segments by the plan of the lane-group
  * sweep (capi_batch.hxx: row_plan_t) and their partial sums added in segment order.  Which lane-group
- * width and which access width serve a call is decided here, once per call. */
-#include "capi_batch.hxx"
+ * width and which access width serve a call is decided here, once per call.  grx_spmm_values is the same
+ * call with the caller's per-entry values where the sweep reads its weights: as they are forward, gathered
+ * into in-entry order through the in-edges' entry ids (graph::transposed_t::edge_ids) transposed. */
+#include "capi_dense.hxx"
 
+#include <gunrock/graph/transpose.hxx>
 #include <gunrock/hip/kernels/spmm_kernels.hxx>
 
 #include <cstdint>
@@ -17,29 +20,6 @@ namespace {
 /// The entries one partial sum takes (a test hook, read per call).
 int32_t segment_entries() {
   return (int32_t)env_or("GRX_SPMM_SEGMENT", k::GROUP_SEGMENT, k::GROUP_SEGMENT_MIN, INT32_MAX);
-}
-
-/// First to last element of a matrix of `rows` rows of F, `ld` apart: [first, last) in bytes.
-struct byte_range_t {
-  unsigned __int128 first, last;
-  byte_range_t(const float* p, std::size_t rows, int64_t ld, int32_t F) {
-    first = (std::uintptr_t)p;
-    const unsigned __int128 elements = rows && F ? (unsigned __int128)(rows - 1) * (unsigned __int128)ld + F : 0;
-    last = first + elements * sizeof(float);
-  }
-  bool empty() const { return last == first; }
-  bool meets(const byte_range_t& o) const { return !empty() && !o.empty() && first < o.last && o.first < last; }
-};
-
-bool sixteen(const float* p, int64_t ld) { return (std::uintptr_t)p % 16 == 0 && ld % k::SPMM_VEC == 0; }
-
-/// Lanes per row: the power of two that covers min(F, a tile) features at four per lane.
-int lanes_for(int32_t F) {
-  const int32_t quads = (std::min<int32_t>(F, k::SPMM_TILE) + k::SPMM_VEC - 1) / k::SPMM_VEC;
-  int L = 1;
-  while (L < quads)
-    L *= 2;
-  return L;
 }
 
 /// The rows of a product, the list of its long ones and the room for their partial sums.
@@ -91,26 +71,39 @@ struct dense_rows_t : row_plan_t {
   }
 };
 
-}  // namespace
-
-extern "C" int grx_spmm(grx_context_t ctx, grx_graph_t g, int32_t transpose, int32_t n_features, const float* d_x,
-                        int64_t ldx, float* d_y, int64_t ldy, const grx_options* opt, grx_stats* stats) {
+/// grx_spmm (`values` false: the handle's values) and grx_spmm_values (the caller's d_values, in the
+/// CSR's entry order) are one call.
+int product_call(const char* call, grx_context_t ctx, grx_graph_t g, bool values, const float* d_values,
+                 int32_t transpose, int32_t n_features, const float* d_x, int64_t ldx, float* d_y, int64_t ldy,
+                 const grx_options* opt, grx_stats* stats) {
+  const std::string name(call);
+  const auto refuse = [&](const char* why) { return invalid((name + ": " + why).c_str()); };
   if (!ctx || !g)
-    return invalid("grx_spmm: NULL argument");
+    return refuse("NULL argument");
   const int32_t F = n_features;
   if (F < 0)
-    return invalid("grx_spmm: n_features < 0");
+    return refuse("n_features < 0");
   if (ldx < F || ldy < F)
-    return invalid("grx_spmm: ldx or ldy is below n_features");
+    return refuse("ldx or ldy is below n_features");
   const std::size_t rows_x = (std::size_t)(transpose ? g->n_rows : g->n_cols);
   const std::size_t rows_y = (std::size_t)(transpose ? g->n_cols : g->n_rows);
   const byte_range_t range_x(d_x, rows_x, ldx, F), range_y(d_y, rows_y, ldy, F);
   if ((!d_x && !range_x.empty()) || (!d_y && !range_y.empty()))
-    return invalid("grx_spmm: d_x or d_y is NULL");
+    return refuse("d_x or d_y is NULL");
   if (range_x.meets(range_y))
-    return invalid("grx_spmm: the byte ranges of d_x and d_y overlap");
+    return refuse("the byte ranges of d_x and d_y overlap");
+  if (values) {
+    if (!d_values && g->nnz > 0)
+      return refuse("d_values is NULL");
+    if (byte_range_t(d_values, (std::size_t)g->nnz, 1, 1).meets(range_y))
+      return refuse("the byte ranges of d_values and d_y overlap");
+  }
   if (transpose && g->n_rows != g->n_cols)
-    return unsupported("grx_spmm: the transposed product of a graph that is not square (n_rows != n_cols)");
+    return unsupported((name + ": the transposed product of a graph that is not square (n_rows != n_cols)").c_str());
+  if (values && transpose && !g->in_edges)  // a mirror entry's value sits elsewhere in d_values
+    return unsupported((name + ": the transposed product with the caller's values needs the in-edges and their "
+                               "entry ids, on a symmetric CSR too: call grx_graph_build_in_edges first")
+                           .c_str());
   const bool timed = effective_options(opt).collect_kernel_time != 0;
   return guarded([&] {
     if (stats)
@@ -119,7 +112,7 @@ extern "C" int grx_spmm(grx_context_t ctx, grx_graph_t g, int32_t transpose, int
       return (int)GRX_OK;
     if (transpose && !g->in_edges)
       if (int rc = ensure_can_pull(ctx, g)) {  // the handle's rows must be its in-rows too
-        last_error() = "grx_spmm: " + last_error();
+        last_error() = name + ": " + last_error();
         return rc;
       }
     auto& sc = ctx->single();
@@ -128,9 +121,20 @@ extern "C" int grx_spmm(grx_context_t ctx, grx_graph_t g, int32_t transpose, int
     int launches = 0;
     {
       dense_rows_t p;
+      hip::device_array_t<float> in_values;  // d_values in the order of the in-entries
       const k::spmm_operands_t m{d_x, ldx, d_y, ldy, F, sixteen(d_y, ldy) ? 1 : 0};
+      k::csr_rows_t rows = transpose ? in_rows(g) : out_rows(g);
       clock.begin_batch();
-      launches += p.build(transpose ? in_rows(g) : out_rows(g), (int32_t)rows_y, g->nnz, segment_entries(), F, sc);
+      if (values && transpose && g->nnz > 0) {
+        in_values = hip::device_array_t<float>((std::size_t)g->nnz);
+        gunrock::graph::detail::gather_kernel<<<grid_for((std::size_t)g->nnz, 256, sc), 256, 0, sc.stream()>>>(
+            d_values, g->in_edges->edge_ids.data(), (long long)g->nnz, in_values.data());
+        rows.ax = in_values.data();
+        ++launches;
+      } else if (values) {
+        rows.ax = d_values;
+      }
+      launches += p.build(rows, (int32_t)rows_y, g->nnz, segment_entries(), F, sc);
       launches += p.product(m, sc);
       GRX_HIP_CHECK(hipGetLastError());
       clock.end_batch();
@@ -146,4 +150,18 @@ extern "C" int grx_spmm(grx_context_t ctx, grx_graph_t g, int32_t transpose, int
     }
     return (int)GRX_OK;
   });
+}
+
+}  // namespace
+
+extern "C" int grx_spmm(grx_context_t ctx, grx_graph_t g, int32_t transpose, int32_t n_features, const float* d_x,
+                        int64_t ldx, float* d_y, int64_t ldy, const grx_options* opt, grx_stats* stats) {
+  return product_call("grx_spmm", ctx, g, false, nullptr, transpose, n_features, d_x, ldx, d_y, ldy, opt, stats);
+}
+
+extern "C" int grx_spmm_values(grx_context_t ctx, grx_graph_t g, const float* d_values, int32_t transpose,
+                               int32_t n_features, const float* d_x, int64_t ldx, float* d_y, int64_t ldy,
+                               const grx_options* opt, grx_stats* stats) {
+  return product_call("grx_spmm_values", ctx, g, true, d_values, transpose, n_features, d_x, ldx, d_y, ldy, opt,
+                      stats);
 }

@@ -905,6 +905,74 @@ int grx_spmv(grx_context_t ctx, grx_graph_t g, int32_t transpose, const float* d
 int grx_spmm(grx_context_t ctx, grx_graph_t g, int32_t transpose, int32_t n_features,
              const float* d_x, int64_t ldx, float* d_y, int64_t ldy,
              const grx_options* opt, grx_stats* stats);
+/* grx_spmm with the caller's per-entry values: Y = A(w) X, where A(w) has the handle's structure and
+ * d_values[e] (device float[nnz], in the order of the CSR's entries, the order of the column array)
+ * in place of the handle's value of entry e.  The handle's own values are not read.  With
+ * grx_sddmm, its derivative, this is a message-passing layer whose edge coefficients are computed
+ * per step (attention, gates, learned edge weights) and their backward pass.  An addition: the
+ * reference has no counterpart.
+ * grx_spmm's whole contract holds with that one substitution -- matrices, leading dimensions, what
+ * is written, values read as they are, the summation order with its hook GRX_SPMM_SEGMENT, stats,
+ * workspace -- and the result is bit for bit what grx_spmm returns on a handle built from the same
+ * structure with those values.
+ * transpose != 0: Y[c, f] = sum over entries e = (r -> c) of X[r, f] * d_values[e], a pull over the
+ * attached in-rows; the call first gathers d_values into in-entry order through the entry ids that
+ * grx_graph_build_in_edges keeps (one more launch, 4 nnz bytes of workspace released on return).
+ * Without in-edges attached the transposed call is GRX_ERR_UNSUPPORTED and the message names
+ * grx_graph_build_in_edges -- on a handle known to be symmetric too: its rows are its in-rows
+ * structurally, but the value of the mirror entry (c -> r) sits elsewhere in d_values, and only the
+ * entry ids say where.  transpose != 0 with n_rows != n_cols is GRX_ERR_UNSUPPORTED.
+ * GRX_ERR_INVALID_ARGUMENT, found on the host before anything is launched, each message naming
+ * grx_spmm_values: grx_spmm's list; a NULL d_values with nnz > 0; the byte range of d_values
+ * overlapping that of Y.  d_values may overlap X. */
+int grx_spmm_values(grx_context_t ctx, grx_graph_t g, const float* d_values, int32_t transpose,
+                    int32_t n_features, const float* d_x, int64_t ldx, float* d_y, int64_t ldy,
+                    const grx_options* opt, grx_stats* stats);
+/* Sampled dense-dense product: one dot product per entry of the handle's CSR,
+ *   d_out[e] = sum over f < F of U[row(e), f] * V[col(e), f],
+ * at the entry's position e in the column array: the edge scores of an attention or gating layer,
+ * and the gradient of grx_spmm_values with respect to its values (U = the incoming gradient, V = X).
+ * An addition: the reference has no counterpart.
+ * F = n_features.  U and V are row-major float32: row i of U starts at d_u + i * ldu and U has n_rows
+ * rows; row j of V starts at d_v + j * ldv and V has n_cols rows; ldu, ldv >= F in elements.  A
+ * rectangular graph is allowed.  U and V may overlap or be the same matrix.  d_out has exactly nnz
+ * elements, all overwritten; nothing before or after them is touched.  Columns [F, ld) of U and V are
+ * never read.  The handle's values are not read and in-edges are not needed; duplicate entries of a
+ * row each get their own, identical result.  Features are read as they are (0 * inf is NaN).
+ * Summation order (the reproducibility contract): no float atomics.  The features are cut into tiles
+ * of 256 consecutive features, the last one may be shorter.  Within a tile of n features let L be
+ * the smallest power of two >= ceil(n / 4).  Lane l of L owns features 4 l .. 4 l + 3 of the tile; its
+ * partial starts from 0.0f and takes those of its features that lie below F in ascending order, one
+ * fused multiply-add each: p = fma(U[r, f], V[c, f], p) (a lane without features keeps 0.0f).  The L
+ * partials are combined by the butterfly p[l] = p[l] + p[l ^ d] for d = L / 2, L / 4, ..., 1 with
+ * plain float32 adds; float32 addition is commutative bit for bit, so every lane ends with the same
+ * value, the tile's sum.  Tile sums are added in ascending tile order, ((t0 + t1) + t2) + ...
+ * The order is a function of F alone: it does not depend on the row, its length or layout, on
+ * GRX_SDDMM_SEGMENT (default 512, minimum 64; an environment variable read per call, a test hook:
+ * the entries of a longer row are handed to several lane groups), on ldu, ldv, the pointers'
+ * alignment, the grid, the CU count or arrival order.  So two calls return the same bits, an entry's
+ * result is that of a one-row graph holding only its row, and where every term and every partial sum
+ * is representable in float32 the result is the exact value.
+ * F == 0: every d_out[e] = 0.0f.  nnz == 0 is GRX_OK: nothing is launched, stats (when given) is
+ * zeroed.
+ * GRX_ERR_INVALID_ARGUMENT, found on the host before anything is launched, each message naming
+ * grx_sddmm: a NULL ctx or g; n_features < 0; ldu < F or ldv < F; a NULL d_u, d_v or d_out whose
+ * array has elements; the byte range of d_out overlapping that of U or of V (the message says
+ * "overlap"), a range being first element to last element as for grx_spmm.
+ * opt may be NULL; only collect_kernel_time is read.  stats may be NULL; set: elapsed_ms,
+ * advance_kernel_ms (with collect_kernel_time), advance_launches (kernel launches: 1 for a graph of
+ * at most GRX_SDDMM_SEGMENT entries, otherwise 3 -- the plan, the short rows, the long rows' items;
+ * 0 for F == 0, which is a memset), iterations = 1, edges_traversed = edges_expanded = nnz;
+ * everything else 0.
+ * The call runs on the caller's CSR and numbering as given, builds and uses no hot-first copy, leaves
+ * nothing on the handle and releases its workspace when it returns: none for a graph of at most
+ * GRX_SDDMM_SEGMENT entries, otherwise 32 bytes per GRX_SDDMM_SEGMENT entries of the graph (the lists
+ * of long rows and their items).  Every element offset into U and V (row * ld + f) is computed in 64
+ * bits.  Accesses are 16 bytes wide where both base pointers are 16-byte aligned and ldu % 4 == 0 and
+ * ldv % 4 == 0, and narrower otherwise; the result does not depend on it. */
+int grx_sddmm(grx_context_t ctx, grx_graph_t g, int32_t n_features,
+              const float* d_u, int64_t ldu, const float* d_v, int64_t ldv,
+              float* d_out, const grx_options* opt, grx_stats* stats);
 /* HITS: hub and authority scores by power iteration, two pull products per iteration.  It REPLACES
  * the reference's hits.hxx rather than wrapping it: that client does one float atomic per edge in each
  * direction, normalises by an L2 norm and stops on bit-equality of two vectors, so it neither repeats
