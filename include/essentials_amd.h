@@ -258,7 +258,12 @@ int grx_pagerank(grx_context_t ctx, grx_graph_t g, float alpha, float tol, float
  * (n_sources must then be 0).  d_bc: float[V] out, overwritten.  Needs in-edges: an undirected
  * graph or grx_graph_build_in_edges (GRX_ERR_UNSUPPORTED otherwise, as for pull PageRank).
  * bc[v] = 0.5 * sum over sources s of delta_s(v) (Brandes, hop counts, edge weights ignored);
- * the same call on the same handle returns bit-identical values.  opt: read as grx_bfs reads it
+ * the same call on the same handle returns bit-identical values.  All of it is float32 and every
+ * term is non-negative: the relative error of bc[v] grows with the number of roundings on the
+ * paths through v (the longest sums and the depth), not with max |bc|, and a vertex on no shortest
+ * path gets +0.  Shortest-path counts above FLT_MAX, and reciprocals of counts below the normal
+ * range (more than 2^126 paths between two vertices), are outside the contract -- as they are for
+ * the reference's float atomics.  opt: read as grx_bfs reads it
  * for the depth search; max_iterations must be 0.  stats: elapsed_ms (the whole call),
  * iterations (BFS levels), vertices_reached and edges_traversed, each summed over sources. */
 int grx_bc(grx_context_t ctx, grx_graph_t g, const int32_t* h_sources, int32_t n_sources,

@@ -23,6 +23,20 @@
  *                    bc[u] += 0.5 * delta[u].
  * rho[w] = (1 + delta[w]) / sigma[w] is what an edge into w contributes per unit of sigma[u], so
  * the backward sweep gathers one word per edge; level D-1 keeps the forward sweep's 1 / sigma.
+ *
+ * The arithmetic as compiled for gfx950 (floating-point contraction is on by default):
+ *   - delta[u] = fl(sigma[u] * s), the rounded product, and bc[u] = fl(bc[u] + 0.5 * delta[u]);
+ *   - rho[u] = fl(fma(sigma[u], s, 1) / sigma[u]): the product is NOT rounded before the 1 is
+ *     added, so the numerator is fl(1 + sigma[u] * s), not fl(1 + delta[u]) -- the two differ by
+ *     at most one rounding, and not at all when the product is exact;
+ *   - both divisions are the correctly rounded v_div_scale / v_div_fmas / v_div_fixup sequence,
+ *     denormals kept.
+ * Every term of every sum is non-negative, so a sum of c terms taken in any order (zeros of empty
+ * lanes and chunks included) is within c - 1 roundings of the exact sum of its rounded terms: the
+ * relative error of bc[v] grows with the number of roundings on the paths through v, not with
+ * max |bc|.  tests/bc_oracle.py counts them and models the three lines above.
+ * Path counts above FLT_MAX (sigma = inf) and reciprocals below the normal range are outside the
+ * contract, as they are for the reference's float atomics.
  */
 #pragma once
 
