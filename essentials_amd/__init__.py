@@ -8,13 +8,15 @@ HIP library and fails loudly when it is missing.
 """
 from .api import (  # noqa: F401
     Context, Graph, Options, Stats, PartitionedPlan, LoadBalance, FilterAlgorithm, UniquifyAlgorithm, EdgeOp,
-    VertexOp, EngineError, bfs, bfs_multi, ppr, hits, spmv, spmm, spmm_autograd, sddmm, sddmm_autograd, predecessors, path, random_walk, neighbor_sample, NeighborSample, sssp, pagerank, bc, tc, kcore, cc, mst, color, scc, lpa, louvain, modularity, spgemm, truss, advance, filter, uniquify,
+    VertexOp, EngineError, bfs, bfs_multi, ppr, hits, spmv, spmm, spmm_autograd, sddmm, sddmm_autograd, edge_softmax, edge_softmax_backward,
+    edge_softmax_autograd, predecessors, path, random_walk, neighbor_sample, NeighborSample, sssp, pagerank, bc, tc, kcore, cc, mst, color, scc, lpa, louvain, modularity, spgemm, truss, advance, filter, uniquify,
     library_path,
     INT_UNREACHED, FLT_UNREACHED,
 )
 
 __all__ = [
     "Context", "Graph", "Options", "Stats", "PartitionedPlan", "LoadBalance", "FilterAlgorithm", "UniquifyAlgorithm",
-    "EdgeOp", "VertexOp", "EngineError", "bfs", "bfs_multi", "ppr", "hits", "spmv", "spmm", "spmm_autograd", "sddmm", "sddmm_autograd", "predecessors", "path", "random_walk", "neighbor_sample", "NeighborSample", "sssp", "pagerank", "bc", "tc", "kcore", "cc", "mst", "color", "scc",
+    "EdgeOp", "VertexOp", "EngineError", "bfs", "bfs_multi", "ppr", "hits", "spmv", "spmm", "spmm_autograd", "sddmm", "sddmm_autograd", "edge_softmax", "edge_softmax_backward",
+    "edge_softmax_autograd", "predecessors", "path", "random_walk", "neighbor_sample", "NeighborSample", "sssp", "pagerank", "bc", "tc", "kcore", "cc", "mst", "color", "scc",
     "lpa", "louvain", "modularity", "spgemm", "truss", "advance", "filter", "uniquify", "library_path", "INT_UNREACHED", "FLT_UNREACHED",
 ]

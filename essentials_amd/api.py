@@ -236,6 +236,9 @@ _SIGNATURES = {
                                   C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_sddmm": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int64, _VP, C.c_int64, _VP, C.POINTER(_Options),
                             C.POINTER(_Stats)]),
+    "grx_edge_softmax": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(_Options), C.POINTER(_Stats)]),
+    "grx_edge_softmax_backward": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(_Options),
+                                            C.POINTER(_Stats)]),
     "grx_hits": (C.c_int, [_VP, _VP, C.c_float, _VP, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_float),
                            C.POINTER(_Options), C.POINTER(_Stats)]),
     "grx_bfs_predecessors": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -1242,6 +1245,89 @@ def sddmm_autograd(ctx: Context, g: Graph, u, v):
             return grad_u, grad_v
 
     return _Scores.apply(u, v)
+
+
+def _by_column(call: str, by) -> int:
+    if by not in ("row", "column"):
+        raise ValueError(f"{call}: by must be \"row\" or \"column\", not {by!r}")
+    return int(by == "column")
+
+
+def edge_softmax(ctx: Context, g: Graph, scores, by: str = "row", out=None, options: Optional[Options] = None):
+    """out[e] = exp(scores[e] - m) / sum of exp(scores[e'] - m) over the entries e' that share e's row
+    (`by="row"`) or column (`by="column"`), m their largest score -> (float32 out of nnz elements on the
+    device, Stats): the attention coefficients of the scores that `sddmm` returns, in the order `spmm`
+    takes as `values`.
+
+    `scores`: contiguous float32 tensor of nnz elements on the context's device, in the order of the
+    CSR's entries; `out`: the same, allocated when None, overwritten in full; the two must not overlap.
+    The graph's values and column ids are not read.  Every sum has a fixed order
+    (include/essentials_amd.h): the same call returns identical bits, and a group's results are those
+    of a graph that holds nothing but that group.  A group with a NaN or +inf score is NaN throughout,
+    as `torch.softmax` gives; a group whose scores are all -inf gets zeros; an empty group writes
+    nothing.  `by="column"` needs the graph's in-edges (`g.build_in_edges(ctx)`) on every graph, a
+    symmetric one included, and a square graph; EngineError otherwise.  The engine's stream waits for
+    what torch has enqueued.  Options read: collect_kernel_time."""
+    column = _by_column("edge_softmax", by)
+    if scores is None:
+        raise TypeError("edge_softmax: scores must be a float32 torch tensor")
+    scores = _float_vector(ctx, scores, g.nnz, "edge_softmax", "scores")
+    out = _float_vector(ctx, out, g.nnz, "edge_softmax", "out")
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    _check(load_library().grx_edge_softmax(ctx._h, g._h, column, _ptr(scores) if scores.numel() else None,
+                                           _ptr(out) if out.numel() else None, C.byref(o), C.byref(s)),
+           "grx_edge_softmax")
+    return out, Stats._from(s)
+
+
+def edge_softmax_backward(ctx: Context, g: Graph, probabilities, grad, by: str = "row", out=None,
+                          options: Optional[Options] = None):
+    """out[e] = probabilities[e] * (grad[e] - D), D the sum of probabilities[e'] * grad[e'] over the
+    entries e' of e's group -> (float32 out of nnz elements on the device, Stats): the gradient with
+    respect to the scores of `edge_softmax`, given its output and the gradient with respect to that.
+
+    The three vectors are contiguous float32 tensors of nnz elements on the context's device in the
+    order of the CSR's entries; `out` is allocated when None and must not overlap an input, the inputs
+    may be one tensor.  `probabilities` need not be a softmax result.  D is summed in `edge_softmax`'s
+    order, one fused multiply-add per entry; the same call returns identical bits.  `by` as for
+    `edge_softmax`.  Options read: collect_kernel_time."""
+    column = _by_column("edge_softmax_backward", by)
+    if probabilities is None or grad is None:
+        raise TypeError("edge_softmax_backward: probabilities and grad must be float32 torch tensors")
+    probabilities = _float_vector(ctx, probabilities, g.nnz, "edge_softmax_backward", "probabilities")
+    grad = _float_vector(ctx, grad, g.nnz, "edge_softmax_backward", "grad")
+    out = _float_vector(ctx, out, g.nnz, "edge_softmax_backward", "out")
+    o = (options or Options())._c()
+    s = _Stats()
+    ctx.after_torch()
+    none = out.numel() == 0
+    _check(load_library().grx_edge_softmax_backward(ctx._h, g._h, column, None if none else _ptr(probabilities),
+                                                    None if none else _ptr(grad), None if none else _ptr(out),
+                                                    C.byref(o), C.byref(s)), "grx_edge_softmax_backward")
+    return out, Stats._from(s)
+
+
+def edge_softmax_autograd(ctx: Context, g: Graph, scores, by: str = "row"):
+    """`edge_softmax(ctx, g, scores, by)[0]` as a differentiable function of `scores`: the output is
+    saved and the backward pass is `edge_softmax_backward(out, grad)`.  It raises at forward time
+    whatever `edge_softmax` raises."""
+    torch = _torch()
+
+    class _Coefficients(torch.autograd.Function):
+        @staticmethod
+        def forward(fctx, s):
+            out = edge_softmax(ctx, g, s, by)[0]
+            fctx.save_for_backward(out)
+            return out
+
+        @staticmethod
+        def backward(fctx, grad):
+            (out,) = fctx.saved_tensors
+            return edge_softmax_backward(ctx, g, out, grad.contiguous(), by)[0]
+
+    return _Coefficients.apply(scores)
 
 
 def hits(ctx: Context, g: Graph, tol: float = 1e-6, hubs=None, authorities=None, normalized: bool = False,

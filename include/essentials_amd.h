@@ -978,6 +978,66 @@ int grx_spmm_values(grx_context_t ctx, grx_graph_t g, const float* d_values, int
 int grx_sddmm(grx_context_t ctx, grx_graph_t g, int32_t n_features,
               const float* d_u, int64_t ldu, const float* d_v, int64_t ldv,
               float* d_out, const grx_options* opt, grx_stats* stats);
+/* Edge softmax: per-entry scores normalised over the entries that share a row, or a column,
+ *   d_out[e] = exp(s[e] - m) / sum over the group's entries e' of exp(s[e'] - m),  m = max s[e'],
+ * the step between grx_sddmm's scores and grx_spmm_values's coefficients in an attention layer (GAT,
+ * graph transformers; DGL's edge_softmax, PyG's softmax(src, index)).  An addition: the reference has
+ * no counterpart.
+ * d_scores and d_out are device float[nnz] in the order of the CSR's column array -- grx_sddmm's
+ * output, grx_spmm_values's input -- and d_out is overwritten in full; nothing before or after its
+ * nnz elements is touched.  The handle's values and column ids are not read.  A group is the set of
+ * entries of one row (by_column == 0) or of one column (by_column != 0), a column's entries taken in
+ * ascending position in the CSR: the order of the in-rows that grx_graph_build_in_edges builds, which
+ * sorts entry ids stably by destination.  by_column reaches an entry through those entry ids where
+ * it walks; nothing is gathered or scattered in a pass of its own.
+ * Arithmetic (the reproducibility contract): no float atomics.  Per group with entries e_0 .. e_{n-1}
+ * in group order: m is the largest score (a maximum does not depend on order); p[e] = expf(s[e] - m),
+ * one rounded subtraction and the precise exponential; S is the sum of p in grx_spmv's row order: the
+ * group is cut into segments of GRX_SOFTMAX_SEGMENT consecutive entries (default 512, minimum 64; an
+ * environment variable read per call, a test hook), within a segment lane l of 16 adds entries l,
+ * l + 16, ... in order starting from 0.0f, the 16 lane sums meet in the butterfly x[l] = x[l] + x[l ^ d]
+ * for d = 8, 4, 2, 1, and the segment sums are added in segment order, ((0.0f + S0) + S1) + ... for a
+ * group of more than one segment; d_out[e] = p[e] / S, a correctly rounded division.
+ * Edge cases: an empty group writes nothing.  A group that holds a NaN or a +inf score gets NaN in
+ * every entry, as torch.softmax gives -- also when its other scores are all -inf: the maximum
+ * propagates NaN.  A group whose scores are all -inf (fully masked) gets 0.0f in every entry, no NaN.
+ * -inf beside finite scores gives an exact 0 for that entry.  No other group is affected by any of these.
+ * Consequences: the same call returns the same bits.  A group's results depend on that group's
+ * values, its length and the segment alone -- not on the grid, the CU count, the other groups or where
+ * the group sits: they are those of a one-group graph.  Equal scores give exactly 1 / n for n up to
+ * 2^24; adding a constant that leaves every s[e] - m unchanged leaves every bit unchanged.  by_column
+ * on a symmetric CSR whose mirror entries carry equal scores gives the row result at the mirror
+ * positions.
+ * nnz == 0 is GRX_OK: nothing is launched, stats (when given) is zeroed.
+ * GRX_ERR_INVALID_ARGUMENT, found on the host before anything is launched, each message naming the
+ * call: a NULL ctx or g; a NULL d_scores or d_out while nnz > 0; the byte range of d_out overlapping
+ * that of d_scores (the message says "overlap").  GRX_ERR_UNSUPPORTED: by_column without in-edges
+ * attached, on a handle known to be symmetric too (the message names grx_graph_build_in_edges): only
+ * the entry ids say where a column's entries sit; by_column with n_rows != n_cols.
+ * opt may be NULL; only collect_kernel_time is read.  stats may be NULL; set: elapsed_ms,
+ * advance_kernel_ms (with collect_kernel_time), advance_launches (kernel launches: 1 for a graph of
+ * at most GRX_SOFTMAX_SEGMENT entries, otherwise 6 -- the plan, the short groups, and for the long
+ * ones their items' maxima, their items' sums, the totals, the quotients), iterations = 1,
+ * edges_traversed = edges_expanded = nnz; everything else 0.
+ * The call leaves nothing on the handle and releases its workspace when it returns: none for a graph
+ * of at most GRX_SOFTMAX_SEGMENT entries, otherwise 48 bytes per GRX_SOFTMAX_SEGMENT entries of the
+ * graph (the lists of long groups and their items; a partial sum, a total and a maximum per item). */
+int grx_edge_softmax(grx_context_t ctx, grx_graph_t g, int32_t by_column, const float* d_scores,
+                     float* d_out, const grx_options* opt, grx_stats* stats);
+/* The derivative of grx_edge_softmax: with a = d_probabilities (its output) and t = d_grad (the
+ * gradient with respect to that output), the gradient with respect to the scores,
+ *   d_out[e] = a[e] * (t[e] - D),  D = sum over the group's entries e' of a[e'] * t[e'].
+ * Arrays, groups, by_column, the segment hook, refusals (a NULL d_probabilities, d_grad or d_out while
+ * nnz > 0; d_out overlapping either input; the inputs may overlap each other), nnz == 0 and stats are
+ * grx_edge_softmax's; advance_launches is 1, or 5 for a graph of more than GRX_SOFTMAX_SEGMENT
+ * entries (the plan, the short groups, the items' sums, the totals, the results).
+ * Arithmetic: D is summed in the segment, lane and butterfly order of S above, one fused
+ * multiply-add per entry, acc = fma(a[e], t[e], acc) from 0.0f; d_out[e] = a[e] * (t[e] - D) with one
+ * rounded subtraction and one rounded multiplication, not fused.  a need not be a softmax result.
+ * The same call returns the same bits, and a group's results are those of a one-group graph. */
+int grx_edge_softmax_backward(grx_context_t ctx, grx_graph_t g, int32_t by_column,
+                              const float* d_probabilities, const float* d_grad, float* d_out,
+                              const grx_options* opt, grx_stats* stats);
 /* HITS: hub and authority scores by power iteration, two pull products per iteration.  It REPLACES
  * the reference's hits.hxx rather than wrapping it: that client does one float atomic per edge in each
  * direction, normalises by an L2 norm and stops on bit-equality of two vectors, so it neither repeats

@@ -2,7 +2,8 @@
  * @file group_rows.hxx
  * @brief The lane-group pull sweep over weighted CSR rows that the SpMV family (spmv_kernels.hxx) and
  * the tree family (tree_kernels.hxx) share; what is gathered through a column id and what becomes of
- * an entry is the caller's.
+ * an entry is the caller's.  The edge softmax (softmax_kernels.hxx) takes the sweep with a walk over
+ * per-entry arrays alone (group_walk_entries).
  *
  * A 16-lane group takes one row: lane l walks entries l, l + 16, ... in order, GROUP_FLIGHT of them in
  * flight, and the 16 lanes meet in a butterfly.  A wavefront holds four groups, a workgroup sixteen;
@@ -77,6 +78,41 @@ __device__ __forceinline__ void group_walk(const csr_rows_t& rows, int32_t lo, i
     for (int k = 0; k < GROUP_FLIGHT; ++k)
       if (e + k * GROUP_LANES < end)
         consume(c[k], w[k], far[k]);
+  }
+}
+
+/**
+ * @brief Entries [lo, hi) of per-entry arrays by one lane group, group_walk without its column ids:
+ * consume(at, a, b) with a = first[at] and b = second[at] (0 without TWO, which reads no second array),
+ * at = at_of[e] with INDIRECT (the entry's position in the arrays: the in-edges' entry ids) and e
+ * otherwise.  The same lanes meet the same entries in the same order as in group_walk, GROUP_FLIGHT of
+ * them in flight.
+ */
+template <bool INDIRECT, bool TWO, typename consume_t>
+__device__ __forceinline__ void group_walk_entries(const float* first, const float* second, const int32_t* at_of,
+                                                   int32_t lo, int32_t hi, int lane, consume_t&& consume) {
+  for (uint32_t e = (uint32_t)lo + lane, end = (uint32_t)hi; e < end; e += GROUP_LANES * GROUP_FLIGHT) {
+    uint32_t at[GROUP_FLIGHT];
+    float a[GROUP_FLIGHT], b[GROUP_FLIGHT];
+#pragma unroll
+    for (int k = 0; k < GROUP_FLIGHT; ++k) {  // a slot past the end reads nothing
+      at[k] = e + k * GROUP_LANES;
+      if (INDIRECT && at[k] < end)
+        at[k] = (uint32_t)at_of[at[k]];
+    }
+#pragma unroll
+    for (int k = 0; k < GROUP_FLIGHT; ++k) {
+      a[k] = b[k] = 0.0f;
+      if (e + k * GROUP_LANES < end) {
+        a[k] = first[at[k]];
+        if (TWO)
+          b[k] = second[at[k]];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < GROUP_FLIGHT; ++k)
+      if (e + k * GROUP_LANES < end)
+        consume(at[k], a[k], b[k]);
   }
 }
 
